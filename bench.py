@@ -2,6 +2,13 @@
 """Headline benchmark: log-posterior evals/sec, 64 chains x (3x64 tanh MLP) x N=4096 per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dtype f64|f32] [--kind logpost|grad]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the headline line (`value`, `ms_per_step`).
+`--full` adds what takes runs of its own: the median of 5 timed regions (`--regions`), the dominant kernel alone replayed
+behind each region (`roofline`), the secondary measurements (`extras`) and the host CPU baseline (`cpu_baseline`).
+`--dump-outputs DIR` writes what the timed step returned in its last step (`sse.npy`, with `--kind grad` also `grad.npy`;
+all chains of the job, in global chain order) after the timed steps.
 
 One *step* = one lock-step evaluation of the log-posterior of all 64 chains' proposals on this
 GPU (64 evals; `--kind grad`: log-posterior + parameter gradient, the HMC inner step), through
@@ -218,6 +225,65 @@ def extras(op, arch, batches, args):
     return out
 
 
+def roofline(args, arch, nloc, flops, t_max, step_dev_ms, kern, fam, i8, kernel, kpath):
+    """What binds the dispatched kernel, from the kernel-alone replays behind the timed regions (`kern`) and the PMC / traffic
+    figures committed under profiles/ (taken by separate profiler passes, not of this run)."""
+    ach = nloc * flops / (kern["kernel_ms"] * 1e-3) / 1e12
+    peak = PEAK_TFLOPS[args.dtype]
+    # int8 matrix work the sliced kernels execute: 26 kept digit products per 64 x 64 product and 16 rows
+    # (v_mfma_i32_16x16x64_i8: 32768 ops in 16 cycles per SIMD -> 5.03 Pop/s dense on 256 CUs at 2.4 GHz)
+    want_grad = args.kind == "grad"
+    mfmas_per_group = 4 * 26 * (6 if want_grad else 2) + (2 * 6 if want_grad else 0)   # per 16 data rows: 64 x 64 products (+ bias row sums)
+    i8_ops = nloc * (N / 16) * mfmas_per_group * 32768 if i8 else None
+    traffic = traffic_src = None
+    tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+    pfile = os.path.join(ROOT, "profiles", "pmc_busy.json")
+    if os.path.exists(tfile) and nloc == CHAINS:
+        # HBM bytes per launch from separate rocprofv3 --pmc passes (FETCH_SIZE doubled per the gfx950
+        # correction, + WRITE_SIZE), recorded by tools/prof_traffic.sh for this kernel / config: NOT of this run
+        key = f"{args.kind}_{args.dtype}_{kpath}"
+        ent = json.load(open(tfile)).get(key, {})
+        traffic = ent.get("hbm_bytes_per_launch")
+        traffic_src = f"profiles/hbm_traffic.json[{key}] (separate rocprofv3 --pmc passes of this command, round {ent.get('round', '?')})" if traffic else None
+    busy = {}
+    if os.path.exists(pfile):
+        busy = json.load(open(pfile)).get(kernel, {})
+    return dict({
+        # what binds the dispatched kernel: the int8-slice kernels are bound by vector-instruction ISSUE (float64 VALU:
+        # recombination, tanh, slicing) with the hidden GEMMs on the int8 matrix pipe beside it; the float64-MFMA
+        # kernels by the float64 pipe that MFMA and VALU share
+        "bound": "mfma", "bound_detail": "valu+i8mfma" if i8 else ("f64mfma" if fam == "fused" else "f64 valu/mfma + hbm (layer-wise)"),
+        "arith": ("47-bit operand slices (2^-47 of the row / activation scale), exact int8 products, float64 accumulation"
+                  if i8 else args.dtype),
+        # yardstick shared by every kernel of this repo: ALGORITHMIC float64 flops of the evaluation (SURVEY 8d) against
+        # the float64 MFMA peak -- for the int8-slice kernels a float64-EQUIVALENT rate, not work done on that pipe
+        "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
+        "yardstick": "algorithmic float64 flops / kernel time vs the float64 MFMA peak (float64-equivalent for the int8-slice kernels)",
+        "frac_step": nloc * flops / (t_max / args.steps) / 1e12 / peak,
+        "int8_pipe": ({"ops_per_launch": i8_ops, "achieved_pops": i8_ops / (kern["kernel_ms"] * 1e-3) / 1e15, "peak_pops": 5.03,
+                       "frac": i8_ops / (kern["kernel_ms"] * 1e-3) / 1e15 / 5.03} if i8 else None),
+        "pmc": dict(busy, source="profiles/pmc_busy.json (rocprofv3 --pmc passes of this command, committed with the profile "
+                                 "it was taken from; not of this run)") if busy else None,
+        "traffic": traffic, "traffic_source": traffic_src, "flops_per_eval": flops, "evals_per_launch": nloc,
+        "step_device_ms": step_dev_ms}, **kern)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (float64, or float32 where the step computes in it).  An array that would take the
+    dump over 64 MiB keeps a fixed, evenly spaced subset of its rows (chains)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > budget:
+            keep = max(1, budget // max(1, a[0].nbytes))
+            a = a[np.linspace(0, a.shape[0] - 1, keep).astype(np.int64)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,14 +293,19 @@ def parse_args():
                     help="weak: 64 chains per GPU; strong: 64 chains in total, block-partitioned over the GPUs")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--kind", default="logpost", choices=["logpost", "grad"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: 5 timed regions by default, "
+                    "the dominant kernel alone + roofline, the secondary measurements (extras) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last step returned "
+                    "as DIR/<name>.npy (sse; with --kind grad also grad)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (N=1 only)")
     ap.add_argument("--path", default="auto", choices=["auto", "generic", "fused", "fused_dp"],
                     help="kernel family (fused_dp: the float64-MFMA fused kernels, without the sliced int8-product forward)")
     ap.add_argument("--graph", type=int, default=-1, help="capture this many consecutive steps in one HIP graph and "
                     "replay it (0 = direct launches, -1 = the largest divisor of --steps up to 50)")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of EXACTLY --steps steps each (barrier + synchronize on both "
-                    "sides, max over ranks); `value` / `ms_per_step` come from the MEDIAN region, all of them are listed in `config`")
+    ap.add_argument("--regions", type=int, default=None, help="timed regions of EXACTLY --steps steps each (barrier + synchronize on both "
+                    "sides, max over ranks); `value` / `ms_per_step` come from the MEDIAN region, all of them are listed in `config` "
+                    "(default: 1, with --full 5)")
     ap.add_argument("--settle-ms", type=float, default=500.0, help="untimed run of the step before the timed region until the GPU "
                     "clock has settled (it ramps up over the first ~500 launches of a fresh process: the same kernel takes 97 us "
                     "right after start-up and 80 us from then on, profiles/r03_clock_ramp_kernel_trace.txt); 0 = off")
@@ -372,12 +443,13 @@ def main():
     if args.graph:
         assert args.steps % args.graph == 0
         graph, out = capture(run, args.graph)
-    # the dominant kernel ALONE (what rocprofv3 reports for it): for the log-posterior the forward without the arrival
-    # epilogue that adds the row-split partial sums of a chain (qn_mlp_sse_fwd_parts); replayed after EACH timed region,
-    # i.e. interleaved with them at the same clock
-    alone = (lambda W: (op.sse_parts(W), None)) if (not want_grad and op.sse_parts(batches[0]).shape[1] > 1) else run
-    g2n = args.graph if args.graph else 1
-    g2, _ = capture(alone, g2n)
+    if args.full:
+        # the dominant kernel ALONE (what rocprofv3 reports for it): for the log-posterior the forward without the arrival
+        # epilogue that adds the row-split partial sums of a chain (qn_mlp_sse_fwd_parts); replayed after EACH timed region,
+        # i.e. interleaved with them at the same clock
+        alone = (lambda W: (op.sse_parts(W), None)) if (not want_grad and op.sse_parts(batches[0]).shape[1] > 1) else run
+        g2n = args.graph if args.graph else 1
+        g2, _ = capture(alone, g2n)
     # untimed: the step itself, replayed until the clock of a freshly started GPU has settled
     settle_steps = 0
     if args.settle_ms > 0:
@@ -392,8 +464,7 @@ def main():
                 settle_steps += 10
             torch.cuda.synchronize(dev)
     nlaunch = args.steps // args.graph if args.graph else args.steps
-    nrep2 = max(1, args.steps // g2n)
-    regions = max(1, args.regions)
+    regions = max(1, args.regions if args.regions is not None else (5 if args.full else 1))
     el_r, dev_r, kern_r = [], [], []
     for r in range(regions):
         # ---- one timed region: EXACTLY --steps steps between barrier + synchronize on both sides
@@ -412,15 +483,21 @@ def main():
         el_r.append(time.perf_counter() - t0)                                 # this rank's K steps, done and synchronized;
         barrier()                                                            # the closing barrier; MAX over ranks below
         dev_r.append(e0.elapsed_time(e1) / args.steps)                       # device ms per step (HIP events, launch stream)
-        # ---- the kernel alone, same number of steps, right behind the region
-        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        k0.record()
-        for i in range(nrep2):
-            g2.replay()
-        k1.record()
-        torch.cuda.synchronize(dev)
-        kern_r.append(k0.elapsed_time(k1) / (nrep2 * g2n))
-    lp_last = -neg_log_post_from_sse(out[0].cpu().numpy(), N, SIGMA)
+        if args.full:
+            # ---- the kernel alone, same number of steps, right behind the region
+            nrep2 = max(1, args.steps // g2n)
+            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            k0.record()
+            for i in range(nrep2):
+                g2.replay()
+            k1.record()
+            torch.cuda.synchronize(dev)
+            kern_r.append(k0.elapsed_time(k1) / (nrep2 * g2n))
+    # what the timed step returned in its last step (graph: the captured step's output tensors, rewritten by every replay)
+    last = {"sse": out[0].detach().cpu().numpy()}
+    if want_grad:
+        last["grad"] = out[1].detach().cpu().numpy()
+    lp_last = -neg_log_post_from_sse(last["sse"], N, SIGMA)
     assert np.all(np.isfinite(lp_last))
     # region times: MAX over ranks per region, then the MEDIAN region is the one reported
     el_t = torch.tensor(el_r, dtype=torch.float64)
@@ -430,9 +507,10 @@ def main():
         el_t = t.cpu()
     el = float(el_t.median())                                                # (lower median for an even count)
     step_dev_ms = float(np.median(dev_r))
-    kms = np.array(kern_r)
-    kern = {"kernel_ms": float(np.median(kms)), "kernel_ms_min": float(kms.min()), "kernel_ms_median": float(np.median(kms)),
-            "kernel_ms_max": float(kms.max()), "kernel_ms_samples": int(regions), "kernel_steps_per_sample": int(nrep2 * g2n)}
+    if args.full:
+        kms = np.array(kern_r)
+        kern = {"kernel_ms": float(np.median(kms)), "kernel_ms_min": float(kms.min()), "kernel_ms_median": float(np.median(kms)),
+                "kernel_ms_max": float(kms.max()), "kernel_ms_samples": int(regions), "kernel_steps_per_sample": int(nrep2 * g2n)}
 
     t_max = el
     if dist is not None:
@@ -444,15 +522,32 @@ def main():
         dist.all_gather_into_tensor(gathered, send)
         torch.cuda.synchronize(dev)
         assert torch.isfinite(gathered).all()
+        if args.dump_outputs:
+            # every chain's outputs on rank 0, in global chain order (rank r's rows sit at r * nmax in the padded gather)
+            rows = []
+            for r in range(world):
+                a, b = shard_bounds(total, r, world)
+                rows.extend(range(r * nmax, r * nmax + b - a))
+            rows = np.array(rows)
+            last["sse"] = gathered.cpu().numpy()[rows]
+            if want_grad:
+                p = arch.nparams
+                gsend = torch.zeros(nmax * p, device=cdev, dtype=out[1].dtype)
+                gsend[:nloc * p] = out[1].reshape(-1).to(cdev)
+                ggath = torch.empty(world * nmax * p, device=cdev, dtype=out[1].dtype)
+                dist.all_gather_into_tensor(ggath, gsend)
+                torch.cuda.synchronize(dev)
+                last["grad"] = ggath.cpu().numpy().reshape(world * nmax, p)[rows]
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     if rank == 0:
         evals = total * args.steps
         value = evals / t_max
         flops = arch.flops_fwdbwd(N) if want_grad else arch.flops_fwd(N)
-        ach = nloc * flops / (kern["kernel_ms"] * 1e-3) / 1e12
-        peak = PEAK_TFLOPS[args.dtype]
         path = op.path(nloc, N, want_grad)
-        # which kernel the step really dispatches, and what binds it
+        # which kernel the step really dispatches
         fam = {1: "generic", 2: "fused"}.get(path, str(path))
         i8 = fam == "fused" and args.dtype == "f64" and args.path != "fused_dp"
         if fam == "fused":
@@ -460,31 +555,16 @@ def main():
         else:
             kernel = "layer-wise kernels (qn_generic.hip)"
         kpath = {"k_fused_fwd_i8": "fused_i8", "k_fused_bwd_i8": "fused_i8_bwd", "k_fused_fwd_f64": "fused_dp", "k_fused_bwd_f64": "fused_dp_bwd"}.get(kernel, fam)
-        # int8 matrix work the sliced kernels execute: 26 kept digit products per 64 x 64 product and 16 rows
-        # (v_mfma_i32_16x16x64_i8: 32768 ops in 16 cycles per SIMD -> 5.03 Pop/s dense on 256 CUs at 2.4 GHz)
-        mfmas_per_group = 4 * 26 * (6 if want_grad else 2) + (2 * 6 if want_grad else 0)   # per 16 data rows: 64 x 64 products (+ bias row sums)
-        i8_ops = nloc * (N / 16) * mfmas_per_group * 32768 if i8 else None
-        traffic = traffic_src = None
-        tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        pfile = os.path.join(ROOT, "profiles", "pmc_busy.json")
-        if os.path.exists(tfile) and nloc == CHAINS:
-            # HBM bytes per launch from separate rocprofv3 --pmc passes (FETCH_SIZE doubled per the gfx950
-            # correction, + WRITE_SIZE), recorded by tools/prof_traffic.sh for this kernel / config: NOT of this run
-            key = f"{args.kind}_{args.dtype}_{kpath}"
-            ent = json.load(open(tfile)).get(key, {})
-            traffic = ent.get("hbm_bytes_per_launch")
-            traffic_src = f"profiles/hbm_traffic.json[{key}] (separate rocprofv3 --pmc passes of this command, round {ent.get('round', '?')})" if traffic else None
-        busy = {}
-        if os.path.exists(pfile):
-            busy = json.load(open(pfile)).get(kernel, {})
         per_gpu = f"{CHAINS} AMCMC chains/GPU" if args.scaling == "weak" else f"{CHAINS} AMCMC chains in total ({nloc} on rank 0)"
+        value_from = (f"median of {regions} timed regions of {args.steps} steps each" if regions > 1
+                      else f"one timed region of {args.steps} steps")
         cfg = {"workload": f"configs[1]: {per_gpu}, 3x64 tanh MLP (p=8513), N=4096 1-D regression; step = batched "
                            + ("log-posterior+gradient" if want_grad else "log-posterior") + " of all chains",
                "chains_total": total, "chains_rank0": nloc, "N": N, "dims": list(DIMS),
                "kind": args.kind, "kernel_path": kpath, "kernel": kernel, "settle_ms": args.settle_ms, "settle_steps": settle_steps,
                "launch": (f"HIP graph of {args.graph} steps, replayed {args.steps // args.graph}x" if args.graph
                           else "direct launches"),
-               "timed_regions": int(regions), "value_from": f"median of {regions} timed regions of {args.steps} steps each (per region: barrier + synchronize, K steps, synchronize -> this rank's time, closing barrier; MAX over ranks)",
+               "timed_regions": int(regions), "value_from": value_from + " (per region: barrier + synchronize, K steps, synchronize -> this rank's time, closing barrier; MAX over ranks)",
                "region_ms_per_step": [1e3 * float(v) / args.steps for v in el_t],
                "parallelism": f"chains sharded x{world}, no data-path collective, one all_gather at the end"}
         if backend != "nccl" and world > 1:
@@ -497,29 +577,13 @@ def main():
             "warmup": args.warmup, "ms_per_step": 1e3 * t_max / args.steps, "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": cfg,
-            "roofline": dict({
-                # what binds the dispatched kernel: the int8-slice kernels are bound by vector-instruction ISSUE (float64 VALU:
-                # recombination, tanh, slicing) with the hidden GEMMs on the int8 matrix pipe beside it; the float64-MFMA
-                # kernels by the float64 pipe that MFMA and VALU share
-                "bound": "mfma", "bound_detail": "valu+i8mfma" if i8 else ("f64mfma" if fam == "fused" else "f64 valu/mfma + hbm (layer-wise)"),
-                "arith": ("47-bit operand slices (2^-47 of the row / activation scale), exact int8 products, float64 accumulation"
-                          if i8 else args.dtype),
-                # yardstick shared by every kernel of this repo: ALGORITHMIC float64 flops of the evaluation against
-                # the float64 MFMA peak -- for the int8-slice kernels a float64-EQUIVALENT rate, not work done on that pipe
-                "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
-                "yardstick": "algorithmic float64 flops / kernel time vs the float64 MFMA peak (float64-equivalent for the int8-slice kernels)",
-                "frac_step": nloc * flops / (t_max / args.steps) / 1e12 / peak,
-                "int8_pipe": ({"ops_per_launch": i8_ops, "achieved_pops": i8_ops / (kern["kernel_ms"] * 1e-3) / 1e15, "peak_pops": 5.03,
-                               "frac": i8_ops / (kern["kernel_ms"] * 1e-3) / 1e15 / 5.03} if i8 else None),
-                "pmc": dict(busy, source="profiles/pmc_busy.json (rocprofv3 --pmc passes of this command, committed with the profile "
-                                         "it was taken from; not of this run)") if busy else None,
-                "traffic": traffic, "traffic_source": traffic_src, "flops_per_eval": flops, "evals_per_launch": nloc,
-                "step_device_ms": step_dev_ms}, **kern),
         }
-        if world == 1 and not args.no_extras:
-            res["extras"] = extras(op, arch, batches, args)
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(arch, x, y)
+        if args.full:
+            res["roofline"] = roofline(args, arch, nloc, flops, t_max, step_dev_ms, kern, fam, i8, kernel, kpath)
+            if world == 1 and not args.no_extras:
+                res["extras"] = extras(op, arch, batches, args)
+            if world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(arch, x, y)
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()

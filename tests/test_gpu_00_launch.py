@@ -2,6 +2,7 @@
 the GPU (a GPU-initialised process must not start child programs on these boxes).  On a 1-GPU box the ranks share
 cuda:0 and use gloo for the collectives; what is checked is the launch / shard / gather logic:
   * `bench.py --gpus 2` starts its own two ranks and prints ONE JSON line with n_gpus = 2, weak and strong scaling;
+  * a plain `bench.py` run times ONE region of exactly --steps steps and `--dump-outputs` writes what its last step returned;
   * `NN_MCMC.fit(engine='device')` under two ranks equals the single-process run for AMCMC and for HMC (random streams
     keyed by the global chain id), with gather = 'all' and gather = 'root'."""
 import json
@@ -9,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -37,10 +39,11 @@ def _json_lines(text):
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
-def test_bench_gpus_2_starts_two_ranks(scaling):
+def test_bench_gpus_2_starts_two_ranks(scaling, tmp_path):
     _no_gpu_yet()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", scaling, "--steps", "20",
-                        "--warmup", "2", "--regions", "3"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--warmup", "2", "--regions", "3", "--full", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -51,6 +54,40 @@ def test_bench_gpus_2_starts_two_ranks(scaling):
     assert d["value"] > 0 and d["roofline"]["kernel_ms_min"] <= d["roofline"]["kernel_ms_median"] <= d["roofline"]["kernel_ms_max"]
     assert abs(d["value"] - d["config"]["chains_total"] * 20 / (d["ms_per_step"] * 20e-3)) <= 1e-6 * d["value"]
     assert d["config"]["timed_regions"] == 3 and len(d["config"]["region_ms_per_step"]) == 3
+    sse = np.load(tmp_path / "sse.npy")                               # every chain of the job, gathered on rank 0
+    assert sse.shape == (d["config"]["chains_total"],) and np.isfinite(sse).all() and (sse > 0).all()
+
+
+def test_bench_plain_run_times_the_steps_once_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): ONE timed region of exactly --steps steps, the headline fields and nothing that takes runs of
+    its own.  --dump-outputs writes what the last timed step returned (here: SSE and gradient of all 64 chains), which must be
+    the oracle's values for that step's weights (step 19 of a 10-step graph replayed twice: resident weight batch 9 % 8 = 1)."""
+    _no_gpu_yet()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--graph", "10",
+                        "--kind", "grad", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1
+    d = lines[0]
+    assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert d["steps"] == 20 and d["config"]["timed_regions"] == 1 and len(d["config"]["region_ms_per_step"]) == 1
+    assert not {"roofline", "extras", "cpu_baseline"} & set(d)
+    assert abs(d["value"] - 64 * 20 / (d["ms_per_step"] * 20e-3)) <= 1e-6 * d["value"]
+    sse, grad = np.load(tmp_path / "sse.npy"), np.load(tmp_path / "grad.npy")
+    assert sse.shape == (64,) and sse.dtype == np.float64 and grad.shape == (64, 8513) and grad.dtype == np.float64
+    import bench
+    from oracle import mlp_ref
+    from quinn_amd.ops import neg_log_post_from_sse
+    x, y = bench.synthetic(bench.N, bench.DIMS[0])
+    mod = mlp_ref.build_module(mlp_ref.MLPSpec(bench.DIMS, "tanh"))
+    yd = [v for v in y]
+    for c in (0, 37, 63):
+        W = 0.1 * np.random.RandomState(1000 + c + 100003 * 1).randn(8513)
+        ref = mlp_ref.logpost(mod, W, x, yd, bench.SIGMA)
+        got = -neg_log_post_from_sse(sse[c], bench.N, bench.SIGMA)
+        assert abs(got - ref) <= 1e-11 * abs(ref), (c, got, ref)
+        gref = mlp_ref.logpostgrad(mod, W, x, yd, bench.SIGMA)
+        assert np.max(np.abs(-(0.5 * grad[c] / bench.SIGMA ** 2) - gref)) <= 1e-9 * np.max(np.abs(gref)), c
 
 
 def test_bench_one_rank_with_a_live_rccl_process_group_prints_one_json_line():

@@ -7,7 +7,7 @@ set -o pipefail
 OTHER=${1:?path of the flagged library}
 for i in 1 2; do
   for lib in quinn_amd/lib/libquinn_amd.so "$OTHER"; do
-    QUINN_AMD_LIB=$PWD/$lib python3 bench.py --steps 300 --warmup 20 --kind grad --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
+    QUINN_AMD_LIB=$PWD/$lib python3 bench.py --full --steps 300 --warmup 20 --kind grad --no-extras --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json; r = json.loads(sys.stdin.read()); print('$lib', round(r['value']), 'evals/s  step', r['ms_per_step'], 'ms  kernel', r['roofline']['kernel_ms'], 'ms  frac', round(r['roofline']['frac'], 4))" || exit 1
   done
 done

@@ -4,5 +4,5 @@
 for r in 1 2; do
 for v in base igrp maxilp iter; do
   if [ $v == base ]; then unset QUINN_AMD_LIB; else export QUINN_AMD_LIB=$PWD/quinn_amd/lib/libquinn_amd_$v.so; fi
-  python bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(sys.argv[1], round(r['value']), r['roofline']['kernel_ms'])" $v
+  python bench.py --full --steps 200 --warmup 20 --no-extras --no-cpu-baseline 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(sys.argv[1], round(r['value']), r['roofline']['kernel_ms'])" $v
 done; done
