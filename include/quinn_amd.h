@@ -298,6 +298,23 @@ int qn_hmc_accept(const double* q, const double* grad_q, const double* sse_q, co
  * msc = 2 is a plain GEMM of the centred ensemble and is left to the BLAS of the host side. */
 int qn_pred_moments(const void* Y, int dtype, int64_t M, int64_t K, double* mean_out, double* var_out, void* stream);
 
+/* Curvature of the data term for the Laplace approximation (quinn/solvers/nn_laplace.py:76-122, quinn/nns/nnwrap.py:153-229),
+ * in plain float64 arithmetic (accurate tanh, no int8-slice kernels; the result is inverted by the caller).  Arguments as
+ * qn_mlp_sse_fwdbwd: W [B, p], shared X [N, d] / Y [N, o], optional row_idx [B, Nb]; r_bn = f_{W[b]}(x) - y of row n of member b.
+ *   QN_CURV_HESS_FULL  out [B, p, p]: the exact Hessian d2/dW2 sum_n |r_bn|^2 / 2 (residual curvature included, so it can be
+ *                      indefinite); both triangles are written and the matrix is symmetric bit for bit.  p <= 16384.
+ *   QN_CURV_EF_DIAG    out [B, p]: the empirical-Fisher diagonal (1/Nb) sum_n (d/dW_j |r_bn|^2 / 2)^2.
+ * The 1/sigma^2 (FULL) and 1/sigma^4 (DIAG) scales of the reference's NegLogPost are the caller's.  Any MLP descriptor
+ * (tanh / relu / identity, with or without bias); a residual-network descriptor, an unknown kind or FULL with p > 16384 is
+ * QN_EINVAL with a message.  Sums run in a fixed order with no atomics: two calls give the same bits.
+ * qn_curv_workspace_bytes returns 0 for arguments qn_mlp_curv refuses (qn_last_error() says why); it needs no device. */
+#define QN_CURV_HESS_FULL 0
+#define QN_CURV_EF_DIAG   1
+size_t qn_curv_workspace_bytes(const qn_desc* desc, int kind, int B, int Nb);
+int qn_mlp_curv(const qn_desc* desc, int kind, const double* W, const double* X, const double* Y,
+                const int32_t* row_idx, int B, int N, int Nb, double* out,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic: y[i] = device tanh(x[i]) in float64 (the activation used by every kernel). */
 int qn_debug_tanh(const double* x, double* y, int64_t n, void* stream);
 /* Diagnostic: the variant the fused kernels use when all weights and inputs are finite and bounded

@@ -2,8 +2,9 @@
 
 Mirror of the hot-path members of the reference's `NNWrap` and `nn_p` (quinn/nns/nnwrap.py:9-150,
 330-347): flat-vector <-> parameters (`p_flatten` / `p_unflatten`, parameters() order), prediction
-with a given flat vector, loss and loss-gradient of a `NegLogPost` as numpy values.  The Hessian
-helpers of the reference (nnwrap.py:153-229) belong to the Laplace solver and are out of scope.
+with a given flat vector, loss and loss-gradient of a `NegLogPost` as numpy values, and the curvature
+helpers of the Laplace solver (`calc_hess_full` / `calc_hess_diag`, nnwrap.py:153-229) from the float64
+curvature kernels (`BatchedMLP.curvature`, csrc/qn_curv.hip) instead of one autograd pass per parameter.
 """
 import numpy as np
 import torch
@@ -70,6 +71,28 @@ class NNWrap():
             raise NotImplementedError("calc_lossgrad on the accelerated path takes a quinn_amd NegLogPost")
         self.p_unflatten(weights)
         return loss_fn.value_and_grad(weights, inputs, np.asarray(targets), want_grad=True)[1]
+
+    def _curvature(self, weights, loss_fn, inputs, targets, kind):
+        if not isinstance(loss_fn, NegLogPost):
+            raise NotImplementedError("calc_hess_* on the accelerated path takes a quinn_amd NegLogPost")
+        if loss_fn.priorparams is not None:
+            raise NotImplementedError("calc_hess_* with a prior: the Laplace solver's NegLogPost has none (nn_laplace.py:107)")
+        self.p_unflatten(weights)
+        x = np.asarray(inputs.detach().cpu() if isinstance(inputs, torch.Tensor) else inputs, dtype=np.float64)
+        y = np.asarray(targets.detach().cpu() if isinstance(targets, torch.Tensor) else targets, dtype=np.float64)
+        x = x.reshape(-1, self._arch.dims[0])
+        op = BatchedMLP(self._arch, x, y.reshape(x.shape[0], -1), **self._opargs)
+        return op.curvature(np.asarray(weights, dtype=np.float64).reshape(1, -1), kind)[0].cpu().numpy()
+
+    def calc_hess_full(self, weigths, loss_fn, inputs, targets):
+        """np.ndarray `(p,p)`: exact Hessian of the data term of `loss_fn` (a `NegLogPost` without prior) w.r.t. the flat
+        weights, (1/sigma^2) d2/dW2 sum_n |f(x_n) - y_n|^2 / 2 (nnwrap.py:153-201; residual curvature included)."""
+        return self._curvature(weigths, loss_fn, inputs, targets, "full") / loss_fn.sigma ** 2
+
+    def calc_hess_diag(self, weigths, loss_fn, inputs, targets):
+        """np.ndarray `(p,p)`: diagonal matrix of the empirical Fisher, mean_n (d loss_n / dW)^2 with loss_n the one-row
+        `loss_fn` (nnwrap.py:204-229): (1/sigma^4) mean_n (d/dW |f(x_n) - y_n|^2 / 2)^2."""
+        return np.diag(self._curvature(weigths, loss_fn, inputs, targets, "diag") / loss_fn.sigma ** 4)
 
 
 def nnwrapper(x, nnmodel):

@@ -421,6 +421,48 @@ class BatchedMLP:
         return self._call(W, None, True, False, X=X, Y=Y)[1]
 
 
+    # ------------------------------------------------------------------ curvature (Laplace approximation)
+    def curvature(self, W, kind, row_idx=None):
+        """Curvature of sum_n |f_W(x_n) - y_n|^2 / 2 for every weight vector, float64 device tensor (qn_mlp_curv):
+        kind "full" -> [B, p, p] exact Hessian (symmetric bit for bit); "diag" -> [B, p] empirical-Fisher diagonal
+        (1/Nb) sum_n (d/dW |r_n|^2 / 2)^2.  `row_idx` [B, Nb]: member b sees rows row_idx[b] only."""
+        code = check_curvature_args(self.arch, self.dtype, kind)
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        if row_idx is not None:
+            ridx = torch.as_tensor(np.asarray(row_idx), device=self.device).to(torch.int32).contiguous().reshape(B, -1)
+            Nb = ridx.shape[1]
+        else:
+            ridx, Nb = None, self.N
+        shape = (B, self.p, self.p) if code == _lib.CURV_HESS_FULL else (B, self.p)
+        out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        if B == 0:
+            return out
+        nbytes = int(self._L.qn_curv_workspace_bytes(self._desc, code, B, Nb))
+        if nbytes == 0:
+            raise QuinnAmdError(f"qn_curv_workspace_bytes: {self._L.qn_last_error().decode()}")
+        ws = self._workspace(nbytes)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_mlp_curv(self._desc, code, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
+                                           ridx.data_ptr() if ridx is not None else None, B, self.N, Nb, out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), stream), "qn_mlp_curv")
+        return out
+
+
+def check_curvature_args(arch, dtype, kind):
+    """The `qn_mlp_curv` kind code for "full" / "diag"; refuses what the curvature kernels do not take: float32 (the result
+    is inverted, so it is float64 only), residual networks, other kinds."""
+    codes = {"full": _lib.CURV_HESS_FULL, "diag": _lib.CURV_EF_DIAG}
+    if kind not in codes:
+        raise ValueError(f"curvature kind {kind!r}: 'full' or 'diag'")
+    if dtype != "float64":
+        raise ValueError(f"curvature needs the float64 operator (got dtype {dtype!r}): the Hessian is inverted")
+    if not isinstance(arch, MLPArch):
+        raise NotImplementedError("curvature of residual networks (RNet) is not supported; MLPs only")
+    return codes[kind]
+
+
 def neg_log_post_from_sse(sse, n, sigma):
     """0.5*SSE/sigma^2 + (n/2)*log(2*pi) + n*log(sigma) in float64 with the operation order
     of the reference's NegLogPost.forward (quinn/nns/losses.py:198-200); sse: float64 array."""

@@ -1,1 +1,2 @@
 """Mirror of the reference package of the same name (hot-path members only)."""
+from .nn_laplace import NN_Laplace  # noqa: F401

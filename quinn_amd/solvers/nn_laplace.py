@@ -1,0 +1,135 @@
+"""Laplace approximation around per-member MAP fits.
+
+Mirror of the reference's `NN_Laplace` (quinn/solvers/nn_laplace.py:11-154):
+  1. MAP: every member minimises the negative log-posterior with a Gaussian prior around a random anchor on the rows
+     `np.random.permutation(ntrn)[:int(ntrn*dfrac)]` -- exactly `NN_RMS.fit` (same batched run, same draw order).
+  2. Curvature at the member's FINAL weights on its own rows, with the reference's `NegLogPost(model, ntrn, 0.1, None)`:
+     the data noise is hard-wired to sigma = 0.1 there (a TODO of the reference) and there is no prior.
+       'full':  H = (1/0.1^2) d2/dW2 sum_n |r_n|^2 / 2            (exact Hessian; may be indefinite)
+       'diag':  H = diag( mean_n (d/dW |r_n|^2 / 2)^2 ) / 0.1^4     (empirical Fisher, dense (p,p) like the reference)
+     One `qn_mlp_curv` call covers all members.  cov = inv(H * cov_scale) on the host (numpy), as the reference does.
+  3. Prediction: `jens = np.random.randint(0, nens)`, then `np.random.multivariate_normal(means[jens], cov_mats[jens])`.
+     The draws are replayed in that order with a per-member SVD factor computed once (numpy's own recipe, so the samples
+     equal numpy's bit for bit); the M weight vectors then go through ONE batched device forward.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from ..ops import BatchedMLP
+from .nn_rms import NN_RMS
+
+LA_SIGMA = 0.1          # nn_laplace.py:107: NegLogPost(learner.nnmodel, ntrn, 0.1, None)
+
+
+def mvn_factor(cov):
+    """(factor, psd) of numpy's legacy `multivariate_normal`: x = z @ (sqrt(s)[:, None] * v) + mean with
+    (u, s, v) = svd(cov); psd is numpy's own check (allclose(v.T * s @ v, cov, rtol=atol=1e-8))."""
+    cov = np.asarray(cov).astype(np.double)
+    (_, s, v) = np.linalg.svd(cov)
+    psd = np.allclose(np.dot(v.T * s, v), cov, rtol=1e-8, atol=1e-8)
+    return np.sqrt(s)[:, None] * v, psd
+
+
+def mvn_draw(mean, factor):
+    """One draw of the global numpy generator, as `np.random.multivariate_normal(mean, cov)` makes it."""
+    p = mean.shape[0]
+    x = np.random.standard_normal([p]).reshape(-1, p)
+    x = np.dot(x, factor)
+    x += mean
+    return x.reshape(p)
+
+
+class NN_Laplace(NN_RMS):
+    """Args: nnmodel, la_type ('full' | 'diag'), cov_scale, datanoise (of the MAP fit), priorsigma, and the
+    `NN_Ens` keywords (nens, dfrac, verbose, device, dtype)."""
+
+    def __init__(self, nnmodel, la_type='full', cov_scale=1.0, datanoise=0.1, priorsigma=1.0, **kwargs):
+        super().__init__(nnmodel, datanoise=datanoise, priorsigma=priorsigma, **kwargs)
+        self.la_type = la_type
+        self.cov_scale = cov_scale
+        self.means = []
+        self.cov_mats = []
+        self._factors = []
+
+    def _kind(self):
+        if self.la_type not in ('full', 'diag'):
+            raise NotImplementedError(f"la_type {self.la_type!r}: only 'full' and 'diag' are accepted")
+        return self.la_type
+
+    def _store(self, w, hess):
+        self.means.append(np.asarray(w, dtype=np.float64))
+        self.cov_mats.append(np.linalg.inv(hess * self.cov_scale))
+        self._factors.append(None)
+
+    def _scaled(self, curv):
+        """Reference scaling of the kernels' result (numpy, one member)."""
+        if self.la_type == 'full':
+            return curv / LA_SIGMA ** 2
+        return np.diag(curv / LA_SIGMA ** 4)
+
+    def fit(self, xtrn, ytrn, **kwargs):
+        """MAP fit of every member (`NN_RMS.fit`), then the curvature of all members in one batched call."""
+        kind = self._kind()
+        super().fit(xtrn, ytrn, **kwargs)
+        W = np.asarray(self.fit_results['final_w'], dtype=np.float64)
+        op = BatchedMLP(self.arch, np.asarray(xtrn, dtype=np.float64), np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1),
+                        device=self._device)
+        curv = op.curvature(W, kind, row_idx=self.rows).cpu().numpy()
+        self.hessians = [self._scaled(c) for c in curv]
+        for j in range(self.nens):
+            self._store(W[j], self.hessians[j])
+
+    def la_calc(self, learner, xtrn, ytrn, batch_size=None):
+        """Append the MAP centre and covariance of one learner (nn_laplace.py:76-122): Hessian at the learner's current
+        weights on (xtrn, ytrn); with `batch_size` the sum of the per-batch results, as the reference forms it."""
+        kind = self._kind()
+        from ..ops import flatten_module
+        w = flatten_module(learner.nnmodel)
+        xtrn = np.asarray(xtrn, dtype=np.float64).reshape(len(xtrn), -1)
+        ytrn = np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1)
+        ntrn = len(xtrn)
+        op = BatchedMLP(self.arch, xtrn, ytrn, device=self._device)
+        if not batch_size:
+            hess = self._scaled(op.curvature(w[None], kind)[0].cpu().numpy())
+        else:
+            hess = None
+            for i in range(ntrn // batch_size + 1):
+                j = min(batch_size, ntrn - i * batch_size)
+                if j > 0:
+                    rows = np.arange(i * batch_size, i * batch_size + j, dtype=np.int32)[None]
+                    cur = self._scaled(op.curvature(w[None], kind, row_idx=rows)[0].cpu().numpy())
+                    hess = cur if i == 0 else hess + cur
+        self._store(w, hess)
+        return hess
+
+    # -- prediction ------------------------------------------------------------------------------
+    def _factor(self, j):
+        if self._factors[j] is None:
+            f, psd = mvn_factor(self.cov_mats[j])
+            if not psd:
+                warnings.warn(f"covariance of member {j} is not symmetric positive-semidefinite.", RuntimeWarning)
+            self._factors[j] = f
+        return self._factors[j]
+
+    def _draw_weights(self, nens):
+        """[M, p]: the reference's draws in its order (randint, then the member's multivariate normal) per sample."""
+        W = np.empty((nens, self.nparams))
+        for s in range(nens):
+            jens = np.random.randint(0, self.nens)
+            W[s] = mvn_draw(self.means[jens], self._factor(jens))
+        return W
+
+    def predict_sample(self, x):
+        return self._predict_batch(self._draw_weights(1), x)[0]
+
+    def _predict_ens_dev(self, x, nens=1):
+        return self._predict_batch_dev(self._draw_weights(1 if nens is None else nens), x)
+
+    def predict_ens(self, x, nens=1):
+        """`(M,N,o)`: M draws of `predict_sample` (nn_laplace.py:141-154), evaluated as one batched forward."""
+        return self._predict_ens_dev(x, nens).double().cpu().numpy()
+
+    def predict_ens_fromsamples(self, x, nens=1):
+        return self.predict_ens(x, nens=nens)

@@ -51,6 +51,7 @@ class NN_RMS(NN_Ens):
                           perms=None if perms is None else perms[lo:hi], **kwargs)
         res = {k: all_gather_rows(v, self.nens) for k, v in res.items()}
         self.fit_results, self._best_w, self.anchors = res, res['best_w'], anchors
+        self.rows = rows                                        # member j trained on xtrn[rows[j]]
         for j, learner in enumerate(self.learners):
             load_flat_into(learner.nnmodel, res['final_w'][j])
             learner._best_model, learner._best_w, learner._pred_op = None, res['best_w'][j], None
