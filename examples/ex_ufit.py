@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|vi|ens|rms|laplace} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|vi|ens|rms|laplace|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -19,6 +19,7 @@ from quinn_amd.nns.rnet import RNet, Poly
 from quinn_amd.solvers.nn_ens import NN_Ens
 from quinn_amd.solvers.nn_rms import NN_RMS
 from quinn_amd.solvers.nn_laplace import NN_Laplace
+from quinn_amd.solvers.nn_swag import NN_SWAG
 from quinn_amd.solvers.nn_mcmc import NN_MCMC
 from quinn_amd.solvers.nn_vi import NN_VI
 
@@ -35,7 +36,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'vi', 'ens', 'rms', 'laplace']
+    all_uq_options = ['amcmc', 'hmc', 'vi', 'ens', 'rms', 'laplace', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -77,6 +78,11 @@ def main(meth, quick=False, mlp=False):
         uqnet = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='full')
         uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
         predict = lambda x: uqnet.predict_ens(x, nens=111)
+    elif meth == 'swag':
+        uqnet = NN_SWAG(nnet, nens=3, dfrac=1.0, verbose=not quick, k=10, n_steps=12, c=1, cov_type="lowrank",
+                        lr_swag=0.01)
+        uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
+        predict = lambda x: uqnet.predict_ens(x, nens=111)
     else:
         uqnet = NN_RMS(nnet, nens=7, dfrac=1.0, verbose=not quick, datanoise=datanoise, priorsigma=0.1)
         uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
@@ -89,7 +95,7 @@ def main(meth, quick=False, mlp=False):
     for xg, m, s, t in zip(xgrid[:, 0], ymean, ystd, np.sin(xgrid[:, 0])):
         print(f"  x={xg:+.3f}  mean={m:+.4f}  std={s:.4f}  truth={t:+.4f}")
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
-        if meth in ('vi', 'ens', 'rms', 'laplace') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
+        if meth in ('vi', 'ens', 'rms', 'laplace', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
     return ymean, ystd, rmse
 

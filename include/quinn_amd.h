@@ -315,6 +315,28 @@ int qn_mlp_curv(const qn_desc* desc, int kind, const double* W, const double* X,
                 const int32_t* row_idx, int B, int N, int Nb, double* out,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* SWAG (quinn/solvers/nn_swag.py): the SGD phase of swag_calc and the posterior draws of predict_sample, float64 state.
+ * qn_swag_step: one pass over the B x p parameters of W [B, p]; by mode
+ *   QN_SWAG_INIT          m1 = W, m2 = W * W (G, lr, D unused)
+ *   QN_SWAG_SGD           W -= lr[b] * (G * gscale)  (G [B, p] of dtype gdtype = QN_F64 / QN_F32, lr [B])
+ *   QN_SWAG_SGD_COLLECT   the SGD step, then with the new W and n (the collections already averaged, >= 1, used as a double):
+ *                         m1 = (n m1 + W) / (n + 1),  m2 = (n m2 + W * W) / (n + 1)  and, if D is not NULL, row `slot` of the
+ *                         ring buffer D [B, K, p] gets W - m1 (the updated mean).
+ *   Numpy's order of operations with one rounding each (no contraction, IEEE division): the result equals numpy's bit for bit.
+ * qn_swag_sample: M draws; draw s uses member js[s] (int32 [M], each in [0, B)), z1 [M, p] and, when D is not NULL, z2 [M, K]:
+ *   corr = sqrt(.5) * (sqrt(diag_j) * z1_s) + sqrt(.5) * (D_j z2_s) / sqrt(K - 1)   (D [B, K, p], rows oldest to newest)
+ *   corr = sqrt(diag_j) * z1_s                                                    (D NULL: diagonal covariance)
+ *   theta[s] = mean_j + corr.  drift = 1: mean_j = theta[s] afterwards, in sample order (the reference's in-place
+ *   `theta += corr`); drift = 0: mean is not written.  A negative diag entry gives NaN, as np.sqrt does.  Only D_j z2_s
+ *   is summed in an order of its own; everything else equals numpy's bit for bit.  mean [B, p], diag [B, p], theta [M, p]. */
+#define QN_SWAG_INIT        0
+#define QN_SWAG_SGD         1
+#define QN_SWAG_SGD_COLLECT 2
+int qn_swag_step(int mode, double* W, const void* G, int gdtype, const double* lr, double gscale, double* m1, double* m2,
+                 double* D, int K, int slot, int64_t n, int B, int64_t p, void* stream);
+int qn_swag_sample(double* mean, const double* diag, const double* D, int K, const int32_t* js, const double* z1,
+                   const double* z2, int M, int B, int64_t p, int drift, double* theta, void* stream);
+
 /* Diagnostic: y[i] = device tanh(x[i]) in float64 (the activation used by every kernel). */
 int qn_debug_tanh(const double* x, double* y, int64_t n, void* stream);
 /* Diagnostic: the variant the fused kernels use when all weights and inputs are finite and bounded

@@ -472,3 +472,90 @@ def neg_log_post_from_sse(sse, n, sigma):
     val = val + (n / 2) * np.log(2 * np.float64(np.pi))
     val = val + n * np.log(sig)
     return val
+
+
+# ---------------------------------------------------------------------- SWAG (qn_swag_step / qn_swag_sample)
+def check_swag_args(k, n_steps, c, cov_type):
+    """True for the low-rank covariance, False for the diagonal one (any `cov_type` other than 'lowrank', as in the
+    reference); refuses what NN_SWAG cannot form: k <= 1 (the draw divides by sqrt(k - 1)), c < 1, n_steps < 0 and, for
+    'lowrank', fewer collections n_steps // c than the k deviation columns (the reference fails at prediction then)."""
+    for name, v in (("k", k), ("n_steps", n_steps), ("c", c)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"SWAG {name} must be an integer (got {v!r})")
+    if k <= 1:
+        raise ValueError(f"SWAG k = {k}: need k > 1")
+    if c < 1:
+        raise ValueError(f"SWAG c = {c}: the collection period must be >= 1")
+    if n_steps < 0:
+        raise ValueError(f"SWAG n_steps = {n_steps}: need n_steps >= 0")
+    lowrank = cov_type == "lowrank"
+    if lowrank and n_steps // c < k:
+        raise ValueError(f"SWAG cov_type 'lowrank' needs n_steps // c >= k: {n_steps} // {c} = {n_steps // c} "
+                         f"collections for k = {k} deviation columns")
+    return lowrank
+
+
+def _f64_rows(t, name, B=None, p=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous float64 device tensor is needed")
+    if B is not None and t.shape[0] != B or p is not None and t.shape[-1] != p:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} does not match B = {B}, p = {p}")
+    return t
+
+
+def swag_step(mode, W, G=None, lr=None, gscale=1.0, m1=None, m2=None, D=None, slot=0, n=0):
+    """One `qn_swag_step` pass on the current torch stream.  W, m1, m2: [B, p] float64 device tensors (updated in place);
+    G: [B, p] float64 or float32; lr: [B] float64; D: [B, K, p] float64 ring buffer or None.  mode: `_lib.SWAG_INIT`
+    (m1 = W, m2 = W^2), `_lib.SWAG_SGD`, `_lib.SWAG_SGD_COLLECT` (SGD step, then the moments with count n and D[:, slot])."""
+    B, p = _f64_rows(W, "W").shape
+    for name, t in (("m1", m1), ("m2", m2)):
+        if t is not None:
+            _f64_rows(t, name, B, p)
+    gdt = _lib.QN_F64
+    if G is not None:
+        if G.shape != (B, p) or G.dtype not in (torch.float64, torch.float32) or not G.is_contiguous():
+            raise ValueError("G: a contiguous [B, p] float64 / float32 tensor is needed")
+        gdt = _lib.QN_F64 if G.dtype == torch.float64 else _lib.QN_F32
+    if lr is not None:
+        _f64_rows(lr, "lr", B)
+    K = 0
+    if D is not None:
+        _f64_rows(D, "D", B, p)
+        K = D.shape[1]
+    L = _lib.lib()
+    ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream(W.device).cuda_stream)
+    with torch.cuda.device(W.device):
+        _lib.check(L.qn_swag_step(int(mode), ptr(W), ptr(G), gdt, ptr(lr), float(gscale), ptr(m1), ptr(m2), ptr(D), K,
+                                  int(slot), int(n), B, p, st), "qn_swag_step")
+
+
+def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
+    """`qn_swag_sample` on the current torch stream: theta [M, p] float64 (device) of the M draws with member indices js
+    (host or device ints, each in [0, B)), z1 [M, p], z2 [M, K] (ignored when D is None: diagonal covariance).
+    drift=True moves mean[js[s]] to theta[s] in sample order, as the reference's predict_sample does."""
+    B, p = _f64_rows(mean, "mean").shape
+    _f64_rows(diag, "diag", B, p)
+    dev = mean.device
+    js_h = np.asarray(js.cpu() if isinstance(js, torch.Tensor) else js).reshape(-1)
+    M = js_h.shape[0]
+    if M == 0:
+        return torch.empty(0, p, dtype=torch.float64, device=dev)
+    if js_h.min() < 0 or js_h.max() >= B:
+        raise ValueError(f"member indices must lie in [0, {B})")
+    jsd = torch.as_tensor(js_h.astype(np.int32), device=dev)
+    z1d = _f64_rows(torch.as_tensor(z1, dtype=torch.float64, device=dev).reshape(M, p).contiguous(), "z1", M, p)
+    K, z2d = 0, None
+    if D is not None:
+        _f64_rows(D, "D", B, p)
+        K = D.shape[1]
+        z2d = torch.as_tensor(z2, dtype=torch.float64, device=dev).reshape(M, K).contiguous()
+    if theta is None:
+        theta = torch.empty(M, p, dtype=torch.float64, device=dev)
+    _f64_rows(theta, "theta", M, p)
+    ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().qn_swag_sample(mean.data_ptr(), diag.data_ptr(), ptr(D), K, jsd.data_ptr(), z1d.data_ptr(),
+                                             ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), st), "qn_swag_sample")
+    return theta
