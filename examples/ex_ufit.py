@@ -6,8 +6,9 @@
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
 arguments as the reference example (examples/ex_ufit.py:40-115); differences: many chains run at
-once (`seeds=`), and the matplotlib output is replaced by a printed summary of the predictive
-mean / standard deviation.
+once (`seeds=`), the MCMC branches pool their predictive ensemble over all chains (`chain='all'`)
+and print how well the chains agree (split-R-hat / ESS of parameters, log-posterior and predictions),
+and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
 
@@ -58,13 +59,13 @@ def main(meth, quick=False, mlp=False):
     if meth == 'amcmc':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='amcmc',
-                  sampler_params={'gamma': 0.01}, seeds=range(8))
-        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain=0)
+                  sampler_params={'gamma': 0.01}, seeds=range(8), diagnostics=True)
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
     elif meth == 'hmc':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc',
-                  sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8))
-        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain=0)
+                  sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True)
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
     elif meth == 'vi':
         uqnet = NN_VI(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, val=[xval, yval], datanoise=datanoise, lrate=0.01, batch_size=None, nsam=1,
@@ -97,6 +98,12 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
+    if meth in ('amcmc', 'hmc'):
+        dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
+        for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
+            d = dg[name]
+            print(f"  {label}: max R-hat {np.nanmax(d['rhat']):.3f}  min ESS {np.nanmin(d['ess']):.1f} of {d['n_draws']} draws"
+                  f" ({d['rhat'].size} entries, 8 chains)")
     return ymean, ystd, rmse
 
 

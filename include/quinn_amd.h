@@ -337,6 +337,27 @@ int qn_swag_step(int mode, double* W, const void* G, int gdtype, const double* l
 int qn_swag_sample(double* mean, const double* diag, const double* D, int K, const int32_t* js, const double* z1,
                    const double* z2, int M, int B, int64_t p, int drift, double* theta, void* stream);
 
+/* Multi-chain MCMC diagnostics: the per-chain statistics from which split-R-hat, batch-means ESS and pooled moments follow
+ * (quinn_amd/mcmc/diagnostics.py combines them; the reference runs one chain and has no counterpart).
+ * chain [C, T, K] contiguous, dtype QN_F64 or QN_F32 (a stored chain, a log-posterior trace with K = 1, or the predictions
+ * [C, nens, N * o] of thinned draws).  Rows t0 .. t0 + 2 * nbatch * blen - 1 of every chain are used: two HALVES (h = 0, 1) of
+ * nbatch batches of blen consecutive rows each, n = nbatch * blen rows per half.  stats [C, 6, K] float64; for chain c, entry k:
+ *   row h      mean_h      = mean of the half's n rows
+ *   row 2 + h  M2_h        = sum over the half's rows of (x - mean_h)^2
+ *   row 4 + h  Sb_h        = sum over the half's nbatch batches of (batch mean - mean_h)^2
+ * Float64 accumulation whatever the input type, on shifted values (x minus the first row of its batch; batch means relative to
+ * the first row of the half), so a large common offset costs no digits.  Every batch of every (c, k) is summed by ONE thread in
+ * row order and the batches of a half are merged in batch order: the summation order depends on (nbatch, blen) only -- not on
+ * C, K, t0 or the launch geometry -- there are no atomics, and two calls give the same bits; statistics of a sub-stack of
+ * chains equal the corresponding rows of the whole stack's bit for bit.  A NaN / Inf at (c, t, k) makes rows h, 2 + h, 4 + h of
+ * (c, k) not-finite for the half h that holds t and changes nothing else.
+ * Needs 1 <= C <= 32767, t0 >= 0, nbatch >= 2, blen >= 1, t0 + 2 * nbatch * blen <= T, else QN_EINVAL with a message before any
+ * pointer is touched; qn_chain_stats_workspace_bytes returns 0 for such arguments (qn_last_error() says why) and needs no
+ * device.  The workspace ([C, 2 nbatch, 2, K] float64 batch statistics) needs no initialisation and keeps no state. */
+size_t qn_chain_stats_workspace_bytes(int C, int64_t T, int64_t K, int nbatch, int64_t blen);
+int qn_chain_stats(const void* chain, int dtype, int C, int64_t T, int64_t K, int64_t t0, int nbatch, int64_t blen,
+                   double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic: y[i] = device tanh(x[i]) in float64 (the activation used by every kernel). */
 int qn_debug_tanh(const double* x, double* y, int64_t n, void* stream);
 /* Diagnostic: the variant the fused kernels use when all weights and inputs are finite and bounded

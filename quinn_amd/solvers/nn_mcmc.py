@@ -13,11 +13,13 @@ import copy
 import sys
 
 import numpy as np
+import torch
 from scipy.optimize import minimize
 
 from ..mcmc.admcmc import AMCMC
 from ..mcmc.hmc import HMC
 from ..mcmc.mala import MALA
+from ..mcmc import diagnostics as diag
 from ..ops import BatchedMLP, neg_log_post_from_sse
 from ..parallel import dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
@@ -46,6 +48,7 @@ class NN_MCMC(QUiNNBase):
         self.samples = None
         self.cmode = None
         self.lpinfo = {}
+        self.diagnostics = None
         self._op = None
         self._op_key = None
 
@@ -97,7 +100,8 @@ class NN_MCMC(QUiNNBase):
 
     # -- fit -------------------------------------------------------------------------------
     def fit(self, xtrn, ytrn, zflag=True, datanoise=0.05, nmcmc=6000, param_ini=None, sampler='amcmc',
-            sampler_params=None, *, nchains=1, seeds=None, engine='host', gather='all', gather_chain=None, bfgs_jac=None):
+            sampler_params=None, *, nchains=1, seeds=None, engine='host', gather='all', gather_chain=None, bfgs_jac=None,
+            diagnostics=False, diag_nburn=None):
         """Run MCMC over the flat weight vector.
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
@@ -123,7 +127,15 @@ class NN_MCMC(QUiNNBase):
             bfgs_jac: None -- the `zflag` BFGS pre-fit lets scipy difference the log-posterior, exactly as the reference
             does (nn_mcmc.py:125-127; p + 1 log-posterior evaluations per gradient); 'device' -- the gradient kernel is
             passed as the analytic jacobian (one evaluation per gradient; a different start point than the reference's).
+            diagnostics: True -- after the run, split-R-hat / batch-means ESS / pooled moments of the parameters and of the
+            log-posterior trace over all chains (`quinn_amd.mcmc.diagnostics`), stored as `self.diagnostics = {'params': ...,
+            'logpost': ...}`.  engine='device': one device pass over the engine's own chain tensor before anything is gathered,
+            so it works with gather_chain='none'; host engines: the numpy chain is uploaded in bounded pieces.  Multi-rank:
+            each rank reduces its own chains, the small per-chain statistics follow `gather`.  diag_nburn: rows discarded
+            first (None: nmcmc // 2).  False (default): nothing is computed and `self.diagnostics` is None.
         """
+        self.diagnostics = None
+        diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
         ntrn_, outdim = ytrn.shape
         assert xtrn.shape[0] == ntrn_
         self.lpinfo = {'model': None, 'xd': xtrn, 'yd': [y for y in ytrn], 'ltype': 'classical',
@@ -176,6 +188,9 @@ class NN_MCMC(QUiNNBase):
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
             else:
                 res = empty_results(nmcmc, ini2.shape[1])
+            if diagnostics:
+                # from the engine's device tensors, before they are downloaded (or not: gather_chain='none')
+                self.diagnostics = self._fit_diagnostics(res['chain'], res['logpost'], diag_nburn, ctot, gather)
             # the single collective, at the end, straight from the device tensors (world == 1: a device->host copy)
             res = gather_results(res, ctot, gather, gather_chain)
             self.mcmc_results = res
@@ -201,6 +216,48 @@ class NN_MCMC(QUiNNBase):
         else:
             self.mcmc_results = mymcmc.run(nmcmc=nmcmc, param_ini=param_ini, rngs=rngs, verbose=self.verbose)
         self.samples, self.cmode = self.mcmc_results['chain'], self.mcmc_results['mapparams']
+        if diagnostics:
+            ch, lp = np.asarray(self.mcmc_results['chain']), np.asarray(self.mcmc_results['logpost'])
+            if ch.ndim == 2:
+                ch, lp = ch[None], lp[None]
+            sharded = rngs is not None and dist_info()[1] > 1
+            ctot = nchains if sharded else ch.shape[0]
+            if sharded and ch.shape[0] == ctot:      # gathered chains: every rank reduces its own shard only
+                lo, hi = shard_bounds(ctot)
+                ch, lp = ch[lo:hi], lp[lo:hi]
+            self.diagnostics = self._fit_diagnostics(ch, lp, diag_nburn, ctot if sharded else None, gather)
+
+    def _fit_diagnostics(self, chain, lps, nburn, ctot, gather):
+        """{'params', 'logpost'}: diagnostics of this rank's chains `[C, T, p]` and log-posterior traces `[C, T]`
+        (device tensors or numpy), the per-chain statistics gathered over the ranks as `gather` says."""
+        if chain is None:
+            raise ValueError("diagnostics=True needs the stored chain")
+        dev = self._device
+        return {'params': diag.diagnose_chains(chain, nburn, n_total=ctot, gather=gather, device=dev),
+                'logpost': diag.diagnose_chains(lps[..., None], nburn, n_total=ctot, gather=gather, device=dev)}
+
+    def diagnose(self, x=None, nburn=1000, nens=100):
+        """Diagnostics of `self.samples` (`[C, T, p]`; one 2-D chain counts as C = 1) after `nburn` rows: {'params': ...}
+        as `fit(diagnostics=True)` computes it.  With x `(N, d)` also FUNCTION-SPACE diagnostics under 'pred': `nens` draws
+        per chain thinned by the reference's rule (rows nburn + j * int((T - nburn) / nens)), all C * nens predictions from
+        one batched forward, and the same statistics over the `[C, nens, N * o]` stack; rhat / ess / mean / var there
+        have shape `(N, o)`.  Predictions, unlike weights, do not change when hidden units are permuted."""
+        samples = np.asarray(self.samples)
+        if samples.ndim == 2:
+            samples = samples[None]
+        out = {'params': diag.diagnose_chains(samples, nburn, device=self._device)}
+        if x is not None:
+            C, T, p = samples.shape
+            rows = diag.thinned_rows(T, nens, nburn)
+            y = self._predict_batch_dev(samples[:, rows, :].reshape(C * nens, p), x)        # (C * nens, N, o)
+            N, o = y.shape[1], y.shape[2]
+            if y.dtype not in (torch.float32, torch.float64):
+                y = y.double()
+            pred = diag.diagnose_chains(y.contiguous().view(C, nens, N * o), 0)
+            for k in ('rhat', 'ess', 'mean', 'var'):
+                pred[k] = pred[k].reshape(N, o)
+            out['pred'] = pred
+        return out
 
     # -- prediction --------------------------------------------------------------------------
     def get_best_model(self, param):
@@ -219,11 +276,24 @@ class NN_MCMC(QUiNNBase):
         """`(N,o)` prediction with one flat weight vector (nn_mcmc.py:168-178)."""
         return self._predict_batch(np.asarray(param).reshape(1, -1), x)[0]
 
-    def predict_MAP(self, x):
-        cm = self.cmode if np.ndim(self.cmode) == 1 else self.cmode[0]
+    def predict_MAP(self, x, chain=None):
+        """Prediction with the MAP weights: chain None -- the first chain's (the only one of a reference-style run);
+        'best' -- those of the chain with the largest `maxpost`; an int -- that chain's."""
+        if np.ndim(self.cmode) == 1:
+            cm = self.cmode
+        elif chain == 'best':
+            cm = self.cmode[int(np.argmax(self.mcmc_results['maxpost']))]
+        else:
+            cm = self.cmode[0 if chain is None else chain]
         return self.predict_sample(x, cm)
 
     def _predict_ens_dev(self, x, nens=10, nburn=1000, chain=0):
+        if isinstance(chain, str):
+            if chain != 'all':
+                raise ValueError("chain is an int or 'all'")
+            samples = self.samples if self.samples.ndim == 3 else self.samples[None]
+            picks = diag.pooled_rows(samples.shape[0], samples.shape[1], nens, nburn)
+            return self._predict_batch_dev(np.concatenate([samples[c][rows, :] for c, rows in picks]), x)
         samples = self.samples if self.samples.ndim == 2 else self.samples[chain]
         nevery = int((samples.shape[0] - nburn) / nens)
         rows = [nburn + j * nevery for j in range(nens)]
@@ -232,5 +302,7 @@ class NN_MCMC(QUiNNBase):
     def predict_ens(self, x, nens=10, nburn=1000, chain=0):
         """`(M,N,o)`: predictions with M thinned post-burn-in samples, rows
         nburn + j*int((len-nburn)/nens) of the chain (nn_mcmc.py:194-199) -- one batched
-        forward instead of M sequential ones.  `chain` picks the chain of a multi-chain fit."""
+        forward instead of M sequential ones.  `chain` picks the chain of a multi-chain fit; chain='all' pools the
+        chains: chain c contributes nens // C + (c < nens % C) draws, thinned by the same rule with that count, ordered
+        chain-major, still one batched forward."""
         return self._predict_ens_dev(x, nens, nburn, chain).double().cpu().numpy()

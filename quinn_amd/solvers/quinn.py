@@ -68,16 +68,17 @@ class QUiNNBase():
     def predict(self, x):
         return self.predict_mom_sample(x)[0]
 
-    def predict_mom_sample(self, x, msc=0, nsam=1000):
+    def predict_mom_sample(self, x, msc=0, nsam=1000, **ens_args):
         """Mean `(N,o)`, variance `(N,o)` (ddof=1) and per-output covariance `(N,N,o)` of an
         `nsam`-member predictive ensemble; msc = 0 / 1 / 2 selects how much is computed
         (quinn.py:75-104).  The ensemble stays on the device: mean / variance by `qn_pred_moments`, the
-        covariance as one float64 GEMM of the centred ensemble per output; only the moments are downloaded."""
+        covariance as one float64 GEMM of the centred ensemble per output; only the moments are downloaded.
+        ens_args go to the solver's ensemble (NN_MCMC: `nburn`, `chain`, e.g. chain='all' pools the chains)."""
         if msc not in (0, 1, 2):
             print(f"msc={msc}, but needs to be 0,1, or 2. Exiting.")
             sys.exit()
         dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
-        y = self._predict_ens_dev(x, nsam).to(dev).contiguous()
+        y = self._predict_ens_dev(x, nsam, **ens_args).to(dev).contiguous()
         M, nx, nout = y.shape
         mean = torch.empty(nx, nout, dtype=torch.float64, device=dev)
         var = torch.empty(nx, nout, dtype=torch.float64, device=dev) if msc == 1 else None
