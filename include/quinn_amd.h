@@ -304,16 +304,41 @@ int qn_pred_moments(const void* Y, int dtype, int64_t M, int64_t K, double* mean
  *   QN_CURV_HESS_FULL  out [B, p, p]: the exact Hessian d2/dW2 sum_n |r_bn|^2 / 2 (residual curvature included, so it can be
  *                      indefinite); both triangles are written and the matrix is symmetric bit for bit.  p <= 16384.
  *   QN_CURV_EF_DIAG    out [B, p]: the empirical-Fisher diagonal (1/Nb) sum_n (d/dW_j |r_bn|^2 / 2)^2.
+ *   QN_CURV_GGN_FULL   out [B, p, p]: the generalised Gauss-Newton matrix sum_n sum_k J_nk^T J_nk, J_nk = d f_k(x_n) / dW (the
+ *                      Hessian without its residual term: positive semi-definite by construction); both triangles, symmetric
+ *                      bit for bit.  p <= 16384.
+ *   QN_CURV_GGN_DIAG   out [B, p]: its diagonal sum_n sum_k J_nk[j]^2 -- a SUM over the rows, where EF_DIAG is a MEAN over the
+ *                      rows (and squares the residual-weighted gradient).  No p limit.
+ * The GGN kinds do not read Y (it may be NULL).
  * The 1/sigma^2 (FULL) and 1/sigma^4 (DIAG) scales of the reference's NegLogPost are the caller's.  Any MLP descriptor
- * (tanh / relu / identity, with or without bias); a residual-network descriptor, an unknown kind or FULL with p > 16384 is
+ * (tanh / relu / identity, with or without bias); a residual-network descriptor, an unknown kind or a FULL kind with p > 16384 is
  * QN_EINVAL with a message.  Sums run in a fixed order with no atomics: two calls give the same bits.
  * qn_curv_workspace_bytes returns 0 for arguments qn_mlp_curv refuses (qn_last_error() says why); it needs no device. */
 #define QN_CURV_HESS_FULL 0
 #define QN_CURV_EF_DIAG   1
+#define QN_CURV_GGN_FULL  2
+#define QN_CURV_GGN_DIAG  3
 size_t qn_curv_workspace_bytes(const qn_desc* desc, int kind, int B, int Nb);
 int qn_mlp_curv(const qn_desc* desc, int kind, const double* W, const double* X, const double* Y,
                 const int32_t* row_idx, int B, int N, int Nb, double* out,
                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Linearised ("GLM") predictive of a Gaussian weight posterior N(W[b], Sigma[b]) of an MLP, float64, in closed form:
+ *   mean_out [B, N, o]     f_{W[b]}(x_n)
+ *   cov_out  [B, N, o, o]  J_nk Sigma[b] J_nl^T,  J_nk = d f_k(x_n) / dW at W[b] (flat parameter order)
+ * QN_GLM_COV_FULL: Sigma [B, p, p] (read as given, row P times column Q; meant to be symmetric), p <= 16384;
+ * QN_GLM_COV_DIAG: Sigma [B, p], the diagonal.  X [N, d] are the query points, shared by the members.
+ * J is never stored: T = J Sigma is a GEMM on v_mfma_f64_16x16x4_f64 whose A operand is formed from the per-row backward
+ * signals and layer inputs, and the epilogue contracts each accumulator tile with the matching J entries, so T stays on the
+ * chip as well.  Entries (k, l) and (l, k) are one computed number.  Fixed summation order, no atomics: two calls give the
+ * same bits and the result of a member does not depend on B.  A residual-network descriptor, an unknown cov_kind or
+ * COV_FULL with p > 16384 is QN_EINVAL with a message; qn_glm_workspace_bytes returns 0 for those (qn_last_error() says why)
+ * and needs no device.  The workspace holds B x min(N, 4096) rows of layer inputs and backward signals, never N x p. */
+#define QN_GLM_COV_FULL 0
+#define QN_GLM_COV_DIAG 1
+size_t qn_glm_workspace_bytes(const qn_desc* desc, int cov_kind, int B, int N);
+int qn_mlp_glm_predict(const qn_desc* desc, int cov_kind, const double* W, const double* X, const double* Sigma, int B, int N,
+                       double* mean_out, double* cov_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* SWAG (quinn/solvers/nn_swag.py): the SGD phase of swag_calc and the posterior draws of predict_sample, float64 state.
  * qn_swag_step: one pass over the B x p parameters of W [B, p]; by mode

@@ -2,6 +2,8 @@
 // quinn/nns/nnwrap.py:153-229), float64 only:
 //   QN_CURV_HESS_FULL  out[b] = d2/dW2 sum_n |r_bn|^2 / 2                    [B, p, p], both triangles, exactly symmetric
 //   QN_CURV_EF_DIAG    out[b][j] = (1/Nb) sum_n (d/dW_j |r_bn|^2 / 2)^2        [B, p]
+//   QN_CURV_GGN_FULL   out[b] = sum_n sum_k J_nk^T J_nk,  J_nk = d f_k(x_n)/dW   [B, p, p], both triangles, exactly symmetric
+//   QN_CURV_GGN_DIAG   out[b][j] = sum_n sum_k J_nk[j]^2  (a sum, not a mean)    [B, p]
 //
 // Notation (Linear layer i = 0..L-1, L = nlayers): in_i = input of layer i (in_0 = x), ~in_i = [in_i; 1] (bias slot if any),
 // z_i = W_i in_i + b_i, in_{i+1} = act(z_i), f = z_{L-1}, r = f - y.  Backward: g_{L-1} = r, u_i = W_{i+1}^T g_{i+1},
@@ -17,37 +19,24 @@
 // runs on v_mfma_f64_16x16x4_f64.  Only the entries with row parameter <= column parameter are assembled; a last kernel
 // copies them to the lower triangle, so the result is symmetric bit for bit.
 //
+// GGN.  With g^k the backward pass started from the output unit vector e_k (k_jac_rows, qn_curv_rows.h),
+//   G[(i,a,b),(m,c,d)] = sum_n ~in_i[b] (sum_k g^k_i[a] g^k_m[c]) ~in_m[d]:
+// the FULL assembly with a B operand formed from the per-output signals (no tangents); its diagonal is the DIAG GEMM on
+// sum_k (g^k o g^k) without the division.
+//
 // DIAG.  D_W = (g o g)^T (~in o ~in) / Nb per layer: the weight-gradient GEMM on squared operands, also on the f64 MFMA.
 //
 // Rows are processed in tiles of RT (workspace-bounded); a member's tiles are added into `out` one after another in a fixed
 // order, members one after another: no atomics, two calls give the same bits.  Rows past the end of a tile are zero in every
 // per-row array (so they add exact zeros).
-#include "qn_common.h"
-#include "qn_math.h"
+#include "qn_curv_rows.h"
 
 namespace {
 
 constexpr int CURV_MAX_P = 16384;          // FULL: p x p doubles per member (2.1 GB at the cap)
 constexpr size_t CURV_TANGENT_BUDGET = size_t(1) << 29;   // bytes of tangents per row tile
 constexpr int CURV_RT_MAX = 1024;
-
-struct CurvArgs {
-    int L, act, hb, d, o;
-    int64_t p;
-    int dims[QN_MAX_LAYERS + 1];
-    int64_t offW[QN_MAX_LAYERS], offB[QN_MAX_LAYERS];
-    int offIN[QN_MAX_LAYERS];   // column of ~in_i in a row of IN (width EI)
-    int offG[QN_MAX_LAYERS];    // column of layer i's units in a row of G / SP / S2U / ZG / AD (width D)
-    int EI, D, RT;
-};
-
-typedef double dv4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dv4 mfma64(double a, double b, dv4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// flat index of parameter (layer i, unit a, input slot b); b == dims[i] is the bias slot
-__device__ __forceinline__ int64_t param_index(const CurvArgs& g, int i, int a, int b) {
-    return b < g.dims[i] ? g.offW[i] + (int64_t)a * g.dims[i] + b : g.offB[i] + a;
-}
+constexpr int CURV_RT_GGN = 4096;          // GGN kinds: no tangents, the row tile is bounded by o * RT * D doubles only
 
 // ---- per data row of the tile: forward and backward, stored row-major ([n][column])
 //   IN [RT][EI]: ~in_i;  G [RT][D]: g_i;  SP [RT][D]: act'(z_i);  S2U [RT][D]: act''(z_i) u_i
@@ -67,52 +56,10 @@ __global__ __launch_bounds__(256) void k_curv_rows(CurvArgs g, const double* __r
         return;
     }
     const int64_t row = rows ? rows[n0 + n] : (int64_t)(n0 + n);
-    for (int k = 0; k < g.d; ++k) in[g.offIN[0] + k] = X[row * g.d + k];
-    if (g.hb) in[g.offIN[0] + g.d] = 1.0;
-    for (int i = 0; i < g.L; ++i) {
-        const int hi = g.dims[i], ho = g.dims[i + 1];
-        const double* Wl = W + g.offW[i];
-        const double* x = in + g.offIN[i];
-        for (int j = 0; j < ho; ++j) {
-            double z = 0.0;
-            for (int k = 0; k < hi; ++k) z = fma(Wl[(int64_t)j * hi + k], x[k], z);
-            if (g.hb) z += W[g.offB[i] + j];
-            if (i + 1 < g.L) {
-                double a, d1, d2;
-                if (g.act == QN_ACT_TANH) {
-                    a = qn_tanh_f64(z);
-                    d1 = 1.0 - a * a;
-                    d2 = -2.0 * a * d1;
-                } else if (g.act == QN_ACT_RELU) {
-                    a = qn_relu<double>(z);
-                    d1 = a <= 0.0 ? 0.0 : 1.0;      // the select of the gradient kernels (qn_act_bwd)
-                    d2 = 0.0;
-                } else {
-                    a = z; d1 = 1.0; d2 = 0.0;
-                }
-                in[g.offIN[i + 1] + j] = a;
-                sp[g.offG[i] + j] = d1;
-                s2[g.offG[i] + j] = d2;             // times u_i below
-            } else {
-                gr[g.offG[i] + j] = z - Y[row * g.o + j];
-                sp[g.offG[i] + j] = 1.0;
-                s2[g.offG[i] + j] = 0.0;
-            }
-        }
-        if (i + 1 < g.L && g.hb) in[g.offIN[i + 1] + ho] = 1.0;
-    }
-    for (int i = g.L - 2; i >= 0; --i) {
-        const int hi = g.dims[i + 1], ho = g.dims[i + 2];
-        const double* Wn = W + g.offW[i + 1];
-        const double* gn = gr + g.offG[i + 1];
-        for (int c = 0; c < hi; ++c) {
-            double u = 0.0;
-            for (int j = 0; j < ho; ++j) u = fma(Wn[(int64_t)j * hi + c], gn[j], u);
-            const int col = g.offG[i] + c;
-            gr[col] = qn_act_bwd<double>(u, in[g.offIN[i + 1] + c], g.act);
-            s2[col] *= u;
-        }
-    }
+    double* f = gr + g.offG[g.L - 1];
+    curv_row_forward<true>(g, W, X, row, in, sp, s2, f);
+    for (int j = 0; j < g.o; ++j) f[j] = f[j] - Y[row * g.o + j];
+    curv_row_backward<true>(g, W, in, gr, s2);
 }
 
 // ---- tangents of the directions of layer i, one thread per (direction a = blockIdx.y, row n):
@@ -181,6 +128,9 @@ __global__ __launch_bounds__(64) void k_curv_tangent(CurvArgs g, const double* _
 // One wave = direction a x (64 b) x (4 c) x (16 d): 4 x 4 accumulator tiles of v_mfma_f64_16x16x4_f64, K = rows, 4 per step.
 // Operand maps (one f64 per lane, q = lane >> 4, cl = lane & 15): A[row cl][k q] = ~in_i[b0 + 16 mt + cl] of row n0 + q;
 // B[k q][col cl] = dg_m[c] ~in_m[d0 + cl] + g_m[c] d~in_m[d0 + cl] of that row;  C/D reg r = row q + 4 r, col cl.
+// GGN: the same GEMM with B[k q][col cl] = (sum_k g^k_i[a] g^k_m[c]) ~in_m[d0 + cl]: the sum over the outputs is folded into the
+// operand, so K stays the rows; G is then GK [o][RT][D] of k_jac_rows and ZG / AD are not read.
+template <bool GGN>
 __global__ __launch_bounds__(256) void k_curv_full(CurvArgs g, int i, int m, const double* __restrict__ IN,
                                                    const double* __restrict__ G, const double* __restrict__ ZG,
                                                    const double* __restrict__ AD, double* __restrict__ out, int accumulate) {
@@ -211,16 +161,26 @@ __global__ __launch_bounds__(256) void k_curv_full(CurvArgs g, int i, int m, con
         const int n = n0 + q;
         const double* inr = IN + (size_t)n * g.EI;
         const double* gr = G + (size_t)n * g.D;
-        const double* zr = ZG + (t * g.RT + n) * g.D;
+        const double* zr = GGN ? nullptr : ZG + (t * g.RT + n) * g.D;
         double A[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) A[mt] = inr[g.offIN[i] + bl[mt]];
         const double dv = dlive ? inr[g.offIN[m] + dcol] : 0.0;
-        const double adv = alive ? AD[(t * g.RT + n) * g.D + g.offG[m - 1] + dcol] : 0.0;
+        const double adv = !GGN && alive ? AD[(t * g.RT + n) * g.D + g.offG[m - 1] + dcol] : 0.0;
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) {
             if (cc < ncn) {
-                const double Bv = fma(zr[cidx[cc]], dv, gr[cidx[cc]] * adv);
+                double Bv;
+                if (GGN) {
+                    double s = 0.0;
+                    for (int k = 0; k < g.o; ++k) {
+                        const double* gk = gr + (size_t)k * g.RT * g.D;
+                        s = fma(gk[g.offG[i] + a], gk[cidx[cc]], s);
+                    }
+                    Bv = s * dv;
+                } else {
+                    Bv = fma(zr[cidx[cc]], dv, gr[cidx[cc]] * adv);
+                }
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
                     if (mt < mtn) acc[cc][mt] = mfma64(A[mt], Bv, acc[cc][mt]);
@@ -266,6 +226,8 @@ __global__ __launch_bounds__(256) void k_curv_mirror(double* __restrict__ H, int
 
 // ---- DIAG of layer i over the rows of one tile: one wave = 64 units a x 16 input slots b, K = rows.
 // A[row cl][k q] = g_i[a0 + 16 mt + cl]^2, B[k q][col cl] = ~in_i[b0 + cl]^2; the last tile divides the total by Nb.
+// GGN: A = sum_k g^k_i[.]^2 from GK [o][RT][D], and no division (a sum over the rows).
+template <bool GGN>
 __global__ __launch_bounds__(256) void k_curv_diag(CurvArgs g, int i, const double* __restrict__ IN, const double* __restrict__ G,
                                                    double* __restrict__ out, int accumulate, double div) {
     const int lane = threadIdx.x & 63, q = lane >> 4, cl = lane & 15;
@@ -288,8 +250,18 @@ __global__ __launch_bounds__(256) void k_curv_diag(CurvArgs g, int i, const doub
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             if (mt < mtn) {
-                const double u = G[(size_t)n * g.D + g.offG[i] + al[mt]];
-                acc[mt] = mfma64(u * u, Bv, acc[mt]);
+                double u2;
+                if (GGN) {
+                    u2 = 0.0;
+                    for (int k = 0; k < g.o; ++k) {
+                        const double u = G[((size_t)k * g.RT + n) * g.D + g.offG[i] + al[mt]];
+                        u2 = fma(u, u, u2);
+                    }
+                } else {
+                    const double u = G[(size_t)n * g.D + g.offG[i] + al[mt]];
+                    u2 = u * u;
+                }
+                acc[mt] = mfma64(u2, Bv, acc[mt]);
             }
         }
     }
@@ -309,6 +281,9 @@ __global__ __launch_bounds__(256) void k_curv_diag(CurvArgs g, int i, const doub
     }
 }
 
+bool is_full(int kind) { return kind == QN_CURV_HESS_FULL || kind == QN_CURV_GGN_FULL; }
+bool is_ggn(int kind) { return kind == QN_CURV_GGN_FULL || kind == QN_CURV_GGN_DIAG; }
+
 bool fill_args(const qn_desc* d, int kind, int Nb, CurvArgs* g, const char* who) {
     if (!d) {
         qn_set_error("%s: NULL descriptor", who);
@@ -318,44 +293,30 @@ bool fill_args(const qn_desc* d, int kind, int Nb, CurvArgs* g, const char* who)
         qn_set_error("%s: residual networks (RNet) are not supported; the curvature kernels take an MLP descriptor", who);
         return false;
     }
-    if (kind != QN_CURV_HESS_FULL && kind != QN_CURV_EF_DIAG) {
-        qn_set_error("%s: kind must be QN_CURV_HESS_FULL (0) or QN_CURV_EF_DIAG (1), got %d", who, kind);
+    if (kind != QN_CURV_HESS_FULL && kind != QN_CURV_EF_DIAG && kind != QN_CURV_GGN_FULL && kind != QN_CURV_GGN_DIAG) {
+        qn_set_error("%s: kind must be QN_CURV_HESS_FULL (0), QN_CURV_EF_DIAG (1), QN_CURV_GGN_FULL (2) or QN_CURV_GGN_DIAG (3), "
+                     "got %d", who, kind);
         return false;
     }
-    if (kind == QN_CURV_HESS_FULL && d->p > CURV_MAX_P) {
-        qn_set_error("%s: the full Hessian is refused for p = %lld > %d parameters (%.1f GB per member); use QN_CURV_EF_DIAG",
-                     who, (long long)d->p, CURV_MAX_P, (double)d->p * (double)d->p * 8e-9);
+    if (is_full(kind) && d->p > CURV_MAX_P) {
+        qn_set_error("%s: the full %s is refused for p = %lld > %d parameters (%.1f GB per member); use %s", who,
+                     kind == QN_CURV_HESS_FULL ? "Hessian" : "Gauss-Newton matrix", (long long)d->p, CURV_MAX_P,
+                     (double)d->p * (double)d->p * 8e-9, kind == QN_CURV_HESS_FULL ? "QN_CURV_EF_DIAG" : "QN_CURV_GGN_DIAG");
         return false;
     }
     if (Nb <= 0) {
         qn_set_error("%s: need Nb >= 1 rows", who);
         return false;
     }
-    g->L = d->nlayers;
-    g->act = d->act;
-    g->hb = d->has_bias;
-    g->d = d->dims[0];
-    g->o = d->dims[d->nlayers];
-    g->p = d->p;
-    int ei = 0, dd = 0;
-    for (int i = 0; i <= d->nlayers; ++i) g->dims[i] = d->dims[i];
-    for (int i = 0; i < d->nlayers; ++i) {
-        g->offW[i] = d->offW[i];
-        g->offB[i] = d->offB[i];
-        g->offIN[i] = ei;
-        g->offG[i] = dd;
-        ei += d->dims[i] + d->has_bias;
-        dd += d->dims[i + 1];
-    }
-    g->EI = ei;
-    g->D = dd;
+    curv_fill_dims(d, g);
+    const int dd = g->D;
     const int nb4 = (Nb + 3) / 4 * 4;
     int rt;
     if (kind == QN_CURV_HESS_FULL) {
         const size_t per_row = 2 * (size_t)dd * dd * sizeof(double);
         rt = (int)std::min<size_t>((size_t)CURV_RT_MAX, std::max<size_t>(4, CURV_TANGENT_BUDGET / per_row / 4 * 4));
     } else {
-        rt = 4096;
+        rt = is_ggn(kind) ? CURV_RT_GGN : 4096;
     }
     g->RT = std::min(rt, nb4);
     return true;
@@ -368,9 +329,9 @@ CurvLayout layout(const CurvArgs& g, int kind) {
     size_t off = 0;
     auto take = [&](size_t doubles) { const size_t o = off; off += qn_align(doubles * sizeof(double)); return o; };
     l.in = take((size_t)g.RT * g.EI);
-    l.gr = take((size_t)g.RT * g.D);
-    l.sp = take((size_t)g.RT * g.D);
-    l.s2 = take((size_t)g.RT * g.D);
+    l.gr = take((size_t)g.RT * g.D * (is_ggn(kind) ? g.o : 1));      // GGN: GK [o][RT][D]
+    l.sp = is_ggn(kind) ? 0 : take((size_t)g.RT * g.D);
+    l.s2 = is_ggn(kind) ? 0 : take((size_t)g.RT * g.D);
     l.zg = kind == QN_CURV_HESS_FULL ? take((size_t)g.D * g.RT * g.D) : 0;
     l.ad = kind == QN_CURV_HESS_FULL ? take((size_t)g.D * g.RT * g.D) : 0;
     l.total = off;
@@ -390,8 +351,8 @@ extern "C" int qn_mlp_curv(const qn_desc* d, int kind, const double* W, const do
                            size_t workspace_bytes, void* stream) {
     CurvArgs g;
     if (!fill_args(d, kind, Nb, &g, "qn_mlp_curv")) return QN_EINVAL;
-    if (B <= 0 || N <= 0 || !W || !X || !Y || !out) {
-        qn_set_error("qn_mlp_curv: need B >= 1, N >= 1 and non-NULL W, X, Y, out");
+    if (B <= 0 || N <= 0 || !W || !X || (!Y && !is_ggn(kind)) || !out) {
+        qn_set_error("qn_mlp_curv: need B >= 1, N >= 1 and non-NULL W, X, Y (HESS_FULL / EF_DIAG), out");
         return QN_EINVAL;
     }
     if (!row_idx && Nb != N) {
@@ -416,13 +377,35 @@ extern "C" int qn_mlp_curv(const qn_desc* d, int kind, const double* W, const do
     for (int b = 0; b < B; ++b) {
         const double* Wb = W + (int64_t)b * P;
         const int32_t* rows = row_idx ? row_idx + (int64_t)b * Nb : nullptr;
-        double* ob = out + (kind == QN_CURV_HESS_FULL ? (int64_t)b * P * P : (int64_t)b * P);
+        double* ob = out + (is_full(kind) ? (int64_t)b * P * P : (int64_t)b * P);
         for (int tI = 0; tI < ntiles; ++tI) {
             const int n0 = tI * g.RT, nrows = std::min(g.RT, Nb - n0);
-            hipLaunchKernelGGL(k_curv_rows, dim3((g.RT + 255) / 256), dim3(256), 0, st, g, Wb, X, Y, rows, n0, nrows, IN, G,
-                               SP, S2U);
+            if (is_ggn(kind))
+                hipLaunchKernelGGL(k_jac_rows, dim3((g.RT + 255) / 256, 1), dim3(256), 0, st, g, Wb, X, rows, (int64_t)0, n0,
+                                   nrows, IN, G, (double*)nullptr, (int64_t)0);
+            else
+                hipLaunchKernelGGL(k_curv_rows, dim3((g.RT + 255) / 256), dim3(256), 0, st, g, Wb, X, Y, rows, n0, nrows, IN,
+                                   G, SP, S2U);
             QN_HIP_CHECK(hipGetLastError());
-            if (kind == QN_CURV_HESS_FULL) {
+            if (kind == QN_CURV_GGN_FULL) {
+                for (int i = 0; i < g.L; ++i)
+                    for (int m = i; m < g.L; ++m) {
+                        const int ei = g.dims[i] + g.hb, em = g.dims[m] + g.hb;
+                        const int64_t items = (int64_t)g.dims[i + 1] * ((ei + 63) / 64) * ((g.dims[m + 1] + 3) / 4) *
+                                              ((em + 15) / 16);
+                        hipLaunchKernelGGL(k_curv_full<true>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, g, i, m, IN,
+                                           G, (const double*)nullptr, (const double*)nullptr, ob, tI > 0 ? 1 : 0);
+                        QN_HIP_CHECK(hipGetLastError());
+                    }
+            } else if (kind == QN_CURV_GGN_DIAG) {
+                for (int i = 0; i < g.L; ++i) {
+                    const int ei = g.dims[i] + g.hb;
+                    const int items = ((g.dims[i + 1] + 63) / 64) * ((ei + 15) / 16);
+                    hipLaunchKernelGGL(k_curv_diag<true>, dim3((items + 3) / 4), dim3(256), 0, st, g, i, IN, G, ob,
+                                       tI > 0 ? 1 : 0, 0.0);
+                    QN_HIP_CHECK(hipGetLastError());
+                }
+            } else if (kind == QN_CURV_HESS_FULL) {
                 for (int i = 0; i < g.L; ++i) {
                     hipLaunchKernelGGL(k_curv_tangent, dim3((g.RT + 63) / 64, g.dims[i + 1]), dim3(64), 0, st, g, Wb, i, SP,
                                        S2U, ZG, AD);
@@ -433,7 +416,7 @@ extern "C" int qn_mlp_curv(const qn_desc* d, int kind, const double* W, const do
                         const int ei = g.dims[i] + g.hb, em = g.dims[m] + g.hb;
                         const int64_t items = (int64_t)g.dims[i + 1] * ((ei + 63) / 64) * ((g.dims[m + 1] + 3) / 4) *
                                               ((em + 15) / 16);
-                        hipLaunchKernelGGL(k_curv_full, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, g, i, m, IN, G,
+                        hipLaunchKernelGGL(k_curv_full<false>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, g, i, m, IN, G,
                                            ZG, AD, ob, tI > 0 ? 1 : 0);
                         QN_HIP_CHECK(hipGetLastError());
                     }
@@ -441,13 +424,13 @@ extern "C" int qn_mlp_curv(const qn_desc* d, int kind, const double* W, const do
                 for (int i = 0; i < g.L; ++i) {
                     const int ei = g.dims[i] + g.hb;
                     const int items = ((g.dims[i + 1] + 63) / 64) * ((ei + 15) / 16);
-                    hipLaunchKernelGGL(k_curv_diag, dim3((items + 3) / 4), dim3(256), 0, st, g, i, IN, G, ob, tI > 0 ? 1 : 0,
+                    hipLaunchKernelGGL(k_curv_diag<false>, dim3((items + 3) / 4), dim3(256), 0, st, g, i, IN, G, ob, tI > 0 ? 1 : 0,
                                        tI == ntiles - 1 ? (double)Nb : 0.0);
                     QN_HIP_CHECK(hipGetLastError());
                 }
             }
         }
-        if (kind == QN_CURV_HESS_FULL) {
+        if (is_full(kind)) {
             const unsigned nt = (unsigned)((P + 31) / 32);
             hipLaunchKernelGGL(k_curv_mirror, dim3(nt, nt), dim3(256), 0, st, ob, P);
             QN_HIP_CHECK(hipGetLastError());

@@ -425,7 +425,9 @@ class BatchedMLP:
     def curvature(self, W, kind, row_idx=None):
         """Curvature of sum_n |f_W(x_n) - y_n|^2 / 2 for every weight vector, float64 device tensor (qn_mlp_curv):
         kind "full" -> [B, p, p] exact Hessian (symmetric bit for bit); "diag" -> [B, p] empirical-Fisher diagonal
-        (1/Nb) sum_n (d/dW |r_n|^2 / 2)^2.  `row_idx` [B, Nb]: member b sees rows row_idx[b] only."""
+        (1/Nb) sum_n (d/dW |r_n|^2 / 2)^2; "ggn" -> [B, p, p] generalised Gauss-Newton matrix sum_n sum_k J_nk^T J_nk
+        (J_nk = d f_k(x_n) / dW; positive semi-definite, symmetric bit for bit); "ggn_diag" -> [B, p] its diagonal (a sum over
+        the rows, not a mean).  `row_idx` [B, Nb]: member b sees rows row_idx[b] only."""
         code = check_curvature_args(self.arch, self.dtype, kind)
         Wt = self.weights(W)
         B = Wt.shape[0]
@@ -434,7 +436,7 @@ class BatchedMLP:
             Nb = ridx.shape[1]
         else:
             ridx, Nb = None, self.N
-        shape = (B, self.p, self.p) if code == _lib.CURV_HESS_FULL else (B, self.p)
+        shape = (B, self.p, self.p) if code in (_lib.CURV_HESS_FULL, _lib.CURV_GGN_FULL) else (B, self.p)
         out = torch.empty(shape, dtype=torch.float64, device=self.device)
         if B == 0:
             return out
@@ -449,13 +451,53 @@ class BatchedMLP:
                                            ws.data_ptr(), ws.numel(), stream), "qn_mlp_curv")
         return out
 
+    # ------------------------------------------------------------------ linearised predictive (qn_mlp_glm_predict)
+    def glm_predict(self, W, Sigma, x=None):
+        """Closed-form predictive of the Gaussian weight posteriors N(W[b], Sigma[b]) under the network linearised at W[b]:
+        (mean [B, N, o] = f_{W[b]}(x_n), cov [B, N, o, o] = J_nk Sigma[b] J_nl^T), float64 device tensors.  Sigma [B, p, p]
+        (symmetric) or [B, p] (a diagonal); x defaults to the stored X.  The Jacobian is never stored; B is chunked so the
+        workspace stays under `max_workspace_bytes`; a member's result does not depend on the chunking."""
+        check_curvature_args(self.arch, self.dtype, "ggn")
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        Sg = self._dev(Sigma, torch.float64)
+        if Sg.shape == (B, self.p, self.p):
+            kind = _lib.GLM_COV_FULL
+        elif Sg.shape == (B, self.p):
+            kind = _lib.GLM_COV_DIAG
+        else:
+            raise ValueError(f"Sigma has shape {tuple(Sg.shape)}; expected ({B}, {self.p}, {self.p}) or ({B}, {self.p})")
+        X = self.X if x is None else self._dev(x).reshape(-1, self.arch.dims[0])
+        N, o = X.shape[0], self.arch.dims[-1]
+        mean = torch.empty(B, N, o, dtype=torch.float64, device=self.device)
+        cov = torch.empty(B, N, o, o, dtype=torch.float64, device=self.device)
+        if B == 0 or N == 0:
+            return mean, cov
+        bc = min(B, 65535)
+        while True:
+            nbytes = int(self._L.qn_glm_workspace_bytes(self._desc, kind, bc, N))
+            if nbytes == 0:
+                raise QuinnAmdError(f"qn_glm_workspace_bytes: {self._L.qn_last_error().decode()}")
+            if bc == 1 or nbytes <= self.max_ws:
+                break
+            bc = (bc + 1) // 2
+        ws = self._workspace(nbytes)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, bc):
+                b1 = min(B, b0 + bc)
+                _lib.check(self._L.qn_mlp_glm_predict(self._desc, kind, Wt[b0:b1].data_ptr(), X.data_ptr(), Sg[b0:b1].data_ptr(),
+                                                      b1 - b0, N, mean[b0:b1].data_ptr(), cov[b0:b1].data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), stream), "qn_mlp_glm_predict")
+        return mean, cov
+
 
 def check_curvature_args(arch, dtype, kind):
-    """The `qn_mlp_curv` kind code for "full" / "diag"; refuses what the curvature kernels do not take: float32 (the result
+    """The `qn_mlp_curv` kind code for "full" / "diag" / "ggn" / "ggn_diag"; refuses what the curvature kernels do not take: float32 (the result
     is inverted, so it is float64 only), residual networks, other kinds."""
-    codes = {"full": _lib.CURV_HESS_FULL, "diag": _lib.CURV_EF_DIAG}
+    codes = {"full": _lib.CURV_HESS_FULL, "diag": _lib.CURV_EF_DIAG, "ggn": _lib.CURV_GGN_FULL, "ggn_diag": _lib.CURV_GGN_DIAG}
     if kind not in codes:
-        raise ValueError(f"curvature kind {kind!r}: 'full' or 'diag'")
+        raise ValueError(f"curvature kind {kind!r}: 'full', 'diag', 'ggn' or 'ggn_diag'")
     if dtype != "float64":
         raise ValueError(f"curvature needs the float64 operator (got dtype {dtype!r}): the Hessian is inverted")
     if not isinstance(arch, MLPArch):

@@ -8,9 +8,16 @@ Mirror of the reference's `NN_Laplace` (quinn/solvers/nn_laplace.py:11-154):
        'full':  H = (1/0.1^2) d2/dW2 sum_n |r_n|^2 / 2            (exact Hessian; may be indefinite)
        'diag':  H = diag( mean_n (d/dW |r_n|^2 / 2)^2 ) / 0.1^4     (empirical Fisher, dense (p,p) like the reference)
      One `qn_mlp_curv` call covers all members.  cov = inv(H * cov_scale) on the host (numpy), as the reference does.
+     'ggn' / 'ggn_diag' (no counterpart in the reference): the generalised Gauss-Newton matrix G = sum_n sum_k J_nk^T J_nk of the
+     member's rows (`qn_mlp_curv`, kinds GGN_FULL / GGN_DIAG) with the solver's OWN noise and prior,
+       H = G / datanoise^2 + I / priorsigma^2,
+     the Gauss-Newton Hessian of the objective the member minimised: positive definite by construction.  cov = inv(H * cov_scale)
+     by a Cholesky factorisation on the device, where the covariance also stays for `predict_glm`.
   3. Prediction: `jens = np.random.randint(0, nens)`, then `np.random.multivariate_normal(means[jens], cov_mats[jens])`.
      The draws are replayed in that order with a per-member SVD factor computed once (numpy's own recipe, so the samples
      equal numpy's bit for bit); the M weight vectors then go through ONE batched device forward.
+  4. `predict_glm`: the linearised ("GLM") predictive in closed form -- one `qn_mlp_glm_predict` call gives every member's
+     mean f_b(x_n) and output covariance J Sigma_b J^T; the members' Gaussians are mixed with equal weights.  No draws, no SVD.
 """
 import warnings
 
@@ -41,8 +48,25 @@ def mvn_draw(mean, factor):
     return x.reshape(p)
 
 
+GGN_TYPES = ('ggn', 'ggn_diag')
+
+
+def glm_mixture(f, S, noise_var=0.0):
+    """Moments of the equal-weight mixture of M Gaussians N(f[b, n], S[b, n]) per query point (law of total variance):
+    mean = avg_b f_b,  cov = avg_b (S_b + f_b f_b^T) - mean mean^T, plus noise_var on the diagonal.
+    f (M, N, o), S (M, N, o, o) -> (mean (N, o), cov (N, o, o)), numpy float64."""
+    f = np.asarray(f, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    mean = f.mean(axis=0)
+    second = (S + f[..., :, None] * f[..., None, :]).mean(axis=0)
+    cov = second - mean[:, :, None] * mean[:, None, :]
+    if noise_var:
+        cov = cov + noise_var * np.eye(f.shape[-1])
+    return mean, cov
+
+
 class NN_Laplace(NN_RMS):
-    """Args: nnmodel, la_type ('full' | 'diag'), cov_scale, datanoise (of the MAP fit), priorsigma, and the
+    """Args: nnmodel, la_type ('full' | 'diag' | 'ggn' | 'ggn_diag'), cov_scale, datanoise (of the MAP fit), priorsigma, and the
     `NN_Ens` keywords (nens, dfrac, verbose, device, dtype)."""
 
     def __init__(self, nnmodel, la_type='full', cov_scale=1.0, datanoise=0.1, priorsigma=1.0, **kwargs):
@@ -52,16 +76,47 @@ class NN_Laplace(NN_RMS):
         self.means = []
         self.cov_mats = []
         self._factors = []
+        self._cov_dev = []          # 'ggn': Sigma_j [p, p], 'ggn_diag': its diagonal [p], device float64 (None otherwise)
 
     def _kind(self):
-        if self.la_type not in ('full', 'diag'):
-            raise NotImplementedError(f"la_type {self.la_type!r}: only 'full' and 'diag' are accepted")
+        if self.la_type not in ('full', 'diag') + GGN_TYPES:
+            raise NotImplementedError(f"la_type {self.la_type!r}: only 'full', 'diag', 'ggn' and 'ggn_diag' are accepted")
         return self.la_type
 
     def _store(self, w, hess):
         self.means.append(np.asarray(w, dtype=np.float64))
         self.cov_mats.append(np.linalg.inv(hess * self.cov_scale))
         self._factors.append(None)
+        self._cov_dev.append(None)
+
+    def _store_ggn(self, w, G):
+        """One member of a GGN type from its device curvature G ([p, p] or [p]): H = G / datanoise^2 + I / priorsigma^2,
+        cov = inv(H * cov_scale) by Cholesky on the device.  Returns H (numpy, dense)."""
+        j = len(self.means)
+        prior = 1.0 / self.priorsigma ** 2
+        if self.la_type == 'ggn':
+            H = G / self.datanoise ** 2
+            H.diagonal().add_(prior)
+            chol, info = torch.linalg.cholesky_ex(H * self.cov_scale)
+            if int(info) != 0:
+                raise np.linalg.LinAlgError(f"Cholesky factorisation of the Gauss-Newton Hessian of member {j} failed "
+                                            f"(leading minor {int(info)} is not positive definite)")
+            cov = torch.cholesky_inverse(chol)
+            cov = 0.5 * (cov + cov.mT)
+            cov_np = cov.cpu().numpy()
+            H_np = H.cpu().numpy()
+        else:
+            h = G / self.datanoise ** 2 + prior
+            if not bool(torch.all(h * self.cov_scale > 0)):
+                raise np.linalg.LinAlgError(f"the diagonal Gauss-Newton Hessian of member {j} is not positive")
+            cov = 1.0 / (h * self.cov_scale)
+            cov_np = np.diag(cov.cpu().numpy())
+            H_np = np.diag(h.cpu().numpy())
+        self.means.append(np.asarray(w, dtype=np.float64))
+        self.cov_mats.append(cov_np)
+        self._factors.append(None)
+        self._cov_dev.append(cov)
+        return H_np
 
     def _scaled(self, curv):
         """Reference scaling of the kernels' result (numpy, one member)."""
@@ -76,6 +131,10 @@ class NN_Laplace(NN_RMS):
         W = np.asarray(self.fit_results['final_w'], dtype=np.float64)
         op = BatchedMLP(self.arch, np.asarray(xtrn, dtype=np.float64), np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1),
                         device=self._device)
+        if kind in GGN_TYPES:
+            G = op.curvature(W, kind, row_idx=self.rows)
+            self.hessians = [self._store_ggn(W[j], G[j]) for j in range(self.nens)]
+            return
         curv = op.curvature(W, kind, row_idx=self.rows).cpu().numpy()
         self.hessians = [self._scaled(c) for c in curv]
         for j in range(self.nens):
@@ -91,6 +150,16 @@ class NN_Laplace(NN_RMS):
         ytrn = np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1)
         ntrn = len(xtrn)
         op = BatchedMLP(self.arch, xtrn, ytrn, device=self._device)
+        if kind in GGN_TYPES:                   # the prior enters once, after the per-batch Gauss-Newton sums
+            if not batch_size:
+                G = op.curvature(w[None], kind)[0]
+            else:
+                G = None
+                for i in range(0, ntrn, batch_size):
+                    rows = np.arange(i, min(ntrn, i + batch_size), dtype=np.int32)[None]
+                    cur = op.curvature(w[None], kind, row_idx=rows)[0]
+                    G = cur if G is None else G + cur
+            return self._store_ggn(w, G)
         if not batch_size:
             hess = self._scaled(op.curvature(w[None], kind)[0].cpu().numpy())
         else:
@@ -133,3 +202,34 @@ class NN_Laplace(NN_RMS):
 
     def predict_ens_fromsamples(self, x, nens=1):
         return self.predict_ens(x, nens=nens)
+
+    # -- linearised predictive -------------------------------------------------------------------
+    def predict_glm(self, x, msc=1, noise=False):
+        """Closed-form predictive of the network linearised at each member's MAP weights ("GLM" predictive):
+        member b predicts N(f_b(x_n), J_n Sigma_b J_n^T) and the members are mixed with equal weights (`glm_mixture`).
+        Returns (ymean (N,o), yvar (N,o) | None, ycov (N,o,o) | None); msc = 0 / 1 / 2 selects how much is returned.
+        `ycov` is the covariance ACROSS THE OUTPUTS at each query point -- not `predict_mom_sample`'s (N,N,o), which is the
+        covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal.
+        One `qn_mlp_glm_predict` call over all members; no weight draws and no SVD.  Works for every la_type; with 'full' the
+        covariance may not be positive semi-definite, and negative variances are reported (warned about, not clipped)."""
+        if msc not in (0, 1, 2):
+            raise ValueError(f"msc={msc}, but needs to be 0, 1 or 2")
+        if not self.means:
+            raise RuntimeError("predict_glm needs a fitted solver (fit or la_calc)")
+        x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
+        op = BatchedMLP(self.arch, x, None, device=self._device)
+        diag = self.la_type in ('diag', 'ggn_diag')
+        sig = []
+        for j in range(len(self.means)):
+            c = self._cov_dev[j]
+            if c is None:
+                c = np.diag(self.cov_mats[j]) if diag else self.cov_mats[j]
+                c = torch.as_tensor(np.ascontiguousarray(c), device=op.device)
+            sig.append(c)
+        f, S = op.glm_predict(np.asarray(self.means), torch.stack(sig))
+        mean, cov = glm_mixture(f.cpu().numpy(), S.cpu().numpy(), self.datanoise ** 2 if noise else 0.0)
+        var = np.stack([cov[:, k, k] for k in range(cov.shape[1])], axis=1)
+        if np.any(var < 0):
+            warnings.warn("predict_glm: negative predictive variance (the posterior covariance is not positive "
+                          "semi-definite); values are not clipped.", RuntimeWarning)
+        return mean, (var if msc >= 1 else None), (cov if msc == 2 else None)
