@@ -340,6 +340,30 @@ size_t qn_glm_workspace_bytes(const qn_desc* desc, int cov_kind, int B, int N);
 int qn_mlp_glm_predict(const qn_desc* desc, int cov_kind, const double* W, const double* X, const double* Sigma, int B, int N,
                        double* mean_out, double* cov_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Derivatives with respect to the INPUTS of an MLP, float64 (plain arithmetic, accurate tanh), and the derivative-informed
+ * loss of the reference's GradLoss (quinn/nns/losses.py:84-145) with its weight gradient.  Arguments as qn_mlp_sse_fwdbwd:
+ * W [B, p], shared X [N, d], optional row_idx [B, Nb] (member b sees rows row_idx[b]; without it Nb == N).
+ * qn_mlp_input_jac:  jac_out [B, Nb, o, d] = d f_k(x_n) / d x_j at W[b];  pred_out [B, Nb, o] = f (or NULL).
+ * qn_mlp_sobolev_fwdbwd:  sse_out [B] = sum_n |f - y|^2,  gsse_out [B] = sum_n sum_kj (J_kj - G_kj)^2 (either may be NULL),
+ *   gradW_out [B, p] = wv d sse / dW + wg d gsse / dW, or NULL (values only).  Y [N, o] may be NULL when wv == 0 and
+ *   sse_out == NULL; G [N, o, d], the gradient observations indexed by the same rows as X, may be NULL when wg == 0 and
+ *   gsse_out == NULL.
+ * A data row and its d input tangents are 1 + d rows of one matrix: the tangent forward, the adjoint pass and the weight
+ * gradient (a reverse pass over the forward-mode pass) are matrix products over those rows on v_mfma_f64_16x16x4_f64, with
+ * one fused elementwise kernel per layer and direction in between.  Any MLP descriptor (tanh / relu / identity, with or without
+ * bias) with d <= 16 and o <= 16; a residual-network descriptor, d > 16 or o > 16 is QN_EINVAL with a message before any
+ * pointer is touched, and qn_sobolev_workspace_bytes returns 0 for those (qn_last_error() says why; it needs no device).
+ * Rows go in tiles of at most 2048 (fewer for wide networks: 256 MB of extended rows per member); the workspace is B times
+ * that plus a slab of weight-gradient partial sums, never N x p.  Sums run in a fixed order with no atomics: two calls give
+ * the same bits and a member's result does not depend on B.  want_grad = 0 sizes the workspace of qn_mlp_input_jac and of
+ * qn_mlp_sobolev_fwdbwd without gradW_out. */
+size_t qn_sobolev_workspace_bytes(const qn_desc* desc, int B, int Nb, int want_grad);
+int qn_mlp_input_jac(const qn_desc* desc, const double* W, const double* X, const int32_t* row_idx, int B, int N, int Nb,
+                     double* pred_out, double* jac_out, void* workspace, size_t workspace_bytes, void* stream);
+int qn_mlp_sobolev_fwdbwd(const qn_desc* desc, const double* W, const double* X, const double* Y, const double* G,
+                          const int32_t* row_idx, int B, int N, int Nb, double wv, double wg, double* sse_out,
+                          double* gsse_out, double* gradW_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SWAG (quinn/solvers/nn_swag.py): the SGD phase of swag_calc and the posterior draws of predict_sample, float64 state.
  * qn_swag_step: one pass over the B x p parameters of W [B, p]; by mode
  *   QN_SWAG_INIT          m1 = W, m2 = W * W (G, lr, D unused)

@@ -8,7 +8,7 @@ validation loss; Adam / SGD step), same result dict.  Progress table as in the r
 loss-curve PNG side effects (nnfit.py:195-216) are not reproduced.
 
 Two execution modes
-  * MLP + 'mse' / 'logpost' loss: every member's forward / backward / Adam step is one batched
+  * MLP + 'mse' / 'logpost' / 'gradloss' loss: every member's forward / backward / Adam step is one batched
     kernel launch (`fit_members`); `nnfit` on a single module is the M = 1 case.
   * custom `loss_xy` (NN_VI passes `BNet.viloss`): the reference's loop, driven on the host, with
     the loss evaluated by the HIP kernels inside the callable and `qn_adam_batched` as optimiser.
@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..ops import MLPArch, BatchedMLP, flatten_module
+from ..ops import MLPArch, BatchedMLP, flatten_module, check_gradloss_args
 
 
 def load_flat_into(module, w):
@@ -62,7 +62,7 @@ def draw_perms(nmembers, nepochs, ntrn):
 def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lrate=0.1, wd=0.0,
                 optimizer='adam', loss_fn='mse', datanoise=None, lmbd=None, perm_mode='reference',
                 device=None, dtype='float64', freq_out=100, verbose=True, perms=None, anchors=None,
-                prior_sigma=None, scheduler_lr=None, cooldown=100, factor=0.95):
+                prior_sigma=None, scheduler_lr=None, cooldown=100, factor=0.95, gtrn=None, lam=0.0):
     """Train M members in lock-step.
 
     Args:
@@ -71,7 +71,10 @@ def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lra
         shared by all members (None: each member validates on its own rows); perms: optional precomputed [M, nepochs, ntrn] permutations (a shard of
         `draw_perms` when members are split over ranks); anchors [M,p] + prior_sigma: per-member Gaussian
         prior N(anchor, prior_sigma^2) added to the 'logpost' loss as the reference's NegLogPost does
-        (losses.py:202-204, weight len(batch)/ntrn; used by NN_RMS); the rest as in `nnfit`.
+        (losses.py:202-204, weight len(batch)/ntrn; used by NN_RMS); loss_fn='gradloss' with gtrn (N, d) | (N, o, d), the
+        observed input gradients of the FULL dataset, and lam: the reference's GradLoss (losses.py:84-145),
+        sse(batch) / (n_batch o) + lam gsse(member's rows) / (ntrn o d) -- the penalty is over ALL training rows of the
+        member at every update, and enters the validation and full-training losses too; the rest as in `nnfit`.
     Returns:
         dict with per-member arrays: 'best_w' [M,p], 'final_w' [M,p], 'best_loss' [M],
         'best_epoch' [M], 'best_fepoch' [M], 'history' [M, nupdates, 4].
@@ -88,15 +91,21 @@ def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lra
                 'history': np.zeros((0, nupd, 4))}
     rows = np.asarray(rows).reshape(M, -1)
     o = arch.dims[-1]
+    if loss_fn == 'gradloss':
+        gtrn = check_gradloss_args(arch, dtype, xtrn, gtrn, lam)
     op = BatchedMLP(arch, xtrn, ytrn, device=device, dtype=dtype)
     # xval None: every member validates on its OWN training rows (the reference's nnfit copies the member's
     # subset as the validation set when val is None, nnfit.py:106-109)
     opv = BatchedMLP(arch, xval, yval, device=device, dtype=dtype) if xval is not None else None
     dev = op.device
     nval = opv.N if opv is not None else ntrn
-    if loss_fn == 'mse':
+    cpen = 0.0
+    if loss_fn in ('mse', 'gradloss'):
         tail = lambda sse, n: sse / (n * o)                       # MSELoss(mean), nnfit.py:59-63
         gscale = lambda n: 1.0 / (n * o)
+        if loss_fn == 'gradloss':                                 # + lam * mean over (row, output, input) of (dM/dx - g)^2
+            op.set_grad_data(gtrn)
+            cpen = float(lam) / (ntrn * o * arch.dims[0])
     elif loss_fn == 'logpost':                                    # NegLogPost without prior, losses.py:197-200
         sig = float(datanoise)
         tail = lambda sse, n: 0.5 * sse / sig ** 2 + (n / 2) * np.log(2 * np.pi) + n * np.log(sig)
@@ -145,7 +154,17 @@ def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lra
             idx = torch.gather(rows_d, 1, perm[:, i:i + batch_size]).to(torch.int32)
             nb = idx.shape[1]
             Wc = W if op.tdt == torch.float64 else W.to(op.tdt)
-            sse, g = op.sse_grad(Wc, row_idx=idx)
+            pen = None
+            if loss_fn != 'gradloss':
+                sse, g = op.sse_grad(Wc, row_idx=idx)
+            elif nb == ntrn:                                       # the minibatch is the member's rows: one pass for both terms
+                sse, gsse, g = op.sobolev(W, gscale(nb), cpen, row_idx=idx)
+                pen = cpen * gsse
+            else:
+                sse, _, g = op.sobolev(W, gscale(nb), 0.0, row_idx=idx)
+                _, gsse, gpen = op.sobolev(W, 0.0, cpen, row_idx=rows32)
+                g.add_(gpen)
+                pen = cpen * gsse
             loss_trn = tail(sse, nb)
             # Evaluations the reference makes per update (nnfit.py:133-140): minibatch loss (with gradient), validation loss and --
             # on an epoch's first minibatch -- the loss over the member's whole training subset.  Two of them coincide in common
@@ -165,6 +184,10 @@ def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lra
                 if sse_sub is None:
                     sse_sub = op.sse(Wc, row_idx=rows32)
                 loss_full = tail(sse_sub, ntrn)
+            if pen is not None:                                    # the same penalty in all three losses (GradLoss)
+                loss_trn, loss_val = loss_trn + pen, loss_val + pen
+                if i == 0:
+                    loss_full = loss_full + pen
             gextra = None
             if prior is not None:                                  # NegLogPrior, losses.py:238-256
                 A, sp, cst = prior
@@ -190,7 +213,7 @@ def fit_members(arch, W0, xtrn, ytrn, rows, xval, yval, nepochs, batch_size, lra
                 g = g.double() * gscale(nb) + gextra
                 gs = 1.0
             else:
-                gs = gscale(nb)
+                gs = 1.0 if loss_fn == 'gradloss' else gscale(nb)   # sobolev's gradient carries its weights already
             if optimizer == 'adam':
                 adam_step(W, g, m, v, lr, step, gscale=gs, wd=wd)
             else:
@@ -277,6 +300,14 @@ def nnfit(nnmodel, xtrn, ytrn, val=None, loss_fn='mse', loss_xy=None, datanoise=
         anchors = np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64).reshape(1, -1)
         prior_sigma = float(priorparams['sigma'])
     ntrn = xtrn.shape[0]
+    gradargs = {}
+    if loss_fn == 'gradloss' and loss_xy is None:    # GradLoss: lossparams = {'gtrn': (N, d) | (N, o, d), 'lam': weight}
+        if not isinstance(lossparams, dict) or 'gtrn' not in lossparams:
+            raise ValueError("loss_fn='gradloss' needs lossparams={'gtrn': observed input gradients, 'lam': weight}")
+        if priorparams is not None:
+            raise ValueError("priorparams go with loss_fn='logpost'")
+        lam = lossparams.get('lam', 0.0)
+        gradargs = {'gtrn': check_gradloss_args(MLPArch.from_module(nnmodel), dtype, xtrn, lossparams['gtrn'], lam), 'lam': lam}
     if val is None:
         xval, yval = xtrn.copy(), ytrn.copy()
     else:
@@ -288,7 +319,7 @@ def nnfit(nnmodel, xtrn, ytrn, val=None, loss_fn='mse', loss_xy=None, datanoise=
                           nepochs, batch_size, lrate=lrate, wd=wd, optimizer=optimizer, loss_fn=loss_fn,
                           datanoise=datanoise, lmbd=lmbd, perm_mode=perm_mode, device=device, dtype=dtype,
                           freq_out=freq_out, scheduler_lr=scheduler_lr, cooldown=cooldown, factor=factor,
-                          anchors=anchors, prior_sigma=prior_sigma)
+                          anchors=anchors, prior_sigma=prior_sigma, **gradargs)
         load_flat_into(nnmodel, res['final_w'][0])
         best = copy.deepcopy(nnmodel)
         load_flat_into(best, res['best_w'][0])

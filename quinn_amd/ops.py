@@ -278,6 +278,7 @@ class BatchedMLP:
             self.Y = self._dev(y).reshape(-1, o)
         if self.Y.shape[0] != self.N:
             raise ValueError("x and y row counts differ")
+        self.G = None                                # gradient observations belong to the rows (set_grad_data)
 
     def workspace_bytes(self, B, Nb, want_grad):
         return int(self._L.qn_workspace_bytes(self._desc, B, Nb, int(want_grad), self.qdt))
@@ -490,6 +491,120 @@ class BatchedMLP:
                                                       b1 - b0, N, mean[b0:b1].data_ptr(), cov[b0:b1].data_ptr(), ws.data_ptr(),
                                                       ws.numel(), stream), "qn_mlp_glm_predict")
         return mean, cov
+
+    # ------------------------------------------------------------------ input derivatives (qn_sobolev.hip)
+    def _sobolev_chunk(self, B, Nb, want_grad):
+        """(members per call, workspace bytes): B halved until the workspace fits `max_workspace_bytes`, as `_chunk`."""
+        bc = min(B, 65535)
+        while True:
+            nbytes = int(self._L.qn_sobolev_workspace_bytes(self._desc, bc, Nb, int(want_grad)))
+            if nbytes == 0:
+                raise QuinnAmdError(f"qn_sobolev_workspace_bytes: {self._L.qn_last_error().decode()}")
+            if bc == 1 or nbytes <= self.max_ws:
+                return bc, nbytes
+            bc = (bc + 1) // 2
+
+    def _row_idx(self, row_idx, B):
+        if row_idx is None:
+            return None
+        if not isinstance(row_idx, torch.Tensor):
+            row_idx = np.asarray(row_idx)
+        return torch.as_tensor(row_idx, device=self.device).to(torch.int32).contiguous().reshape(B, -1)
+
+    def input_jacobian(self, W, x=None, want_pred=False):
+        """d f_k(x_n) / d x_j at every weight vector: float64 device tensor [B, N, o, d] (qn_mlp_input_jac); with
+        `want_pred` the pair (jacobian, predictions [B, N, o]) from the same pass.  x defaults to the stored X.  B is chunked
+        so the workspace stays under `max_workspace_bytes`; a member's result does not depend on the chunking."""
+        check_sobolev_args(self.arch, self.dtype)
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        d, o = self.arch.dims[0], self.arch.dims[-1]
+        X = self.X if x is None else self._dev(x).reshape(-1, d)
+        N = X.shape[0]
+        jac = torch.empty(B, N, o, d, dtype=torch.float64, device=self.device)
+        pred = torch.empty(B, N, o, dtype=torch.float64, device=self.device) if want_pred else None
+        if B > 0 and N > 0:
+            bc, nbytes = self._sobolev_chunk(B, N, False)
+            ws = self._workspace(nbytes)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            with torch.cuda.device(self.device):
+                for b0 in range(0, B, bc):
+                    b1 = min(B, b0 + bc)
+                    _lib.check(self._L.qn_mlp_input_jac(self._desc, Wt[b0:b1].data_ptr(), X.data_ptr(), None, b1 - b0, N, N,
+                                                        pred[b0:b1].data_ptr() if pred is not None else None,
+                                                        jac[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                               "qn_mlp_input_jac")
+        return (jac, pred) if want_pred else jac
+
+    def set_grad_data(self, g):
+        """Gradient observations d y_k / d x_j of the stored rows: (N, d) for one output, or (N, o, d)."""
+        check_sobolev_args(self.arch, self.dtype)
+        d, o = self.arch.dims[0], self.arch.dims[-1]
+        G = self._dev(g, torch.float64)
+        if G.numel() != self.N * o * d or G.shape[0] != self.N:
+            raise ValueError(f"gradient data of shape {tuple(G.shape)}: expected ({self.N}, {o}, {d})"
+                             + (f" or ({self.N}, {d})" if o == 1 else ""))
+        self.G = G.reshape(self.N, o, d).contiguous()
+
+    def sobolev(self, W, wv, wg, row_idx=None, want_grad=True):
+        """(sse [B], gsse [B], grad [B, p] or None), float64 device tensors (qn_mlp_sobolev_fwdbwd):
+        sse = sum_n |f - y|^2, gsse = sum_n sum_kj (d f_k / d x_j - G_kj)^2 over the rows (row_idx [B, Nb]: member b sees
+        rows row_idx[b]), grad = wv d sse / dW + wg d gsse / dW.  Needs `set_grad_data`."""
+        check_sobolev_args(self.arch, self.dtype)
+        if getattr(self, "G", None) is None or self.G.shape[0] != self.N:
+            raise ValueError("sobolev: no gradient observations for the stored rows; call set_grad_data(g) first")
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        ridx = self._row_idx(row_idx, B)
+        Nb = ridx.shape[1] if ridx is not None else self.N
+        sse = torch.empty(B, dtype=torch.float64, device=self.device)
+        gsse = torch.empty(B, dtype=torch.float64, device=self.device)
+        grad = torch.empty(B, self.p, dtype=torch.float64, device=self.device) if want_grad else None
+        if B == 0:
+            return sse, gsse, grad
+        bc, nbytes = self._sobolev_chunk(B, Nb, want_grad)
+        ws = self._workspace(nbytes)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, bc):
+                b1 = min(B, b0 + bc)
+                _lib.check(self._L.qn_mlp_sobolev_fwdbwd(
+                    self._desc, Wt[b0:b1].data_ptr(), self.X.data_ptr(), self.Y.data_ptr(), self.G.data_ptr(),
+                    ridx[b0:b1].data_ptr() if ridx is not None else None, b1 - b0, self.N, Nb, float(wv), float(wg),
+                    sse[b0:b1].data_ptr(), gsse[b0:b1].data_ptr(), grad[b0:b1].data_ptr() if want_grad else None,
+                    ws.data_ptr(), ws.numel(), stream), "qn_mlp_sobolev_fwdbwd")
+        return sse, gsse, grad
+
+
+SOBOLEV_MAX_D = SOBOLEV_MAX_O = 16
+
+
+def check_sobolev_args(arch, dtype):
+    """Refuses what the input-derivative kernels (qn_mlp_input_jac / qn_mlp_sobolev_fwdbwd) do not take: float32 (they are
+    float64 only), residual networks, more than 16 inputs or outputs."""
+    if dtype != "float64":
+        raise ValueError(f"input derivatives need the float64 operator (got dtype {dtype!r})")
+    if not isinstance(arch, MLPArch):
+        raise NotImplementedError("input derivatives of residual networks (RNet) are not supported; MLPs only")
+    if arch.dims[0] > SOBOLEV_MAX_D or arch.dims[-1] > SOBOLEV_MAX_O:
+        raise NotImplementedError(f"input derivatives take d <= {SOBOLEV_MAX_D} inputs and o <= {SOBOLEV_MAX_O} outputs "
+                                  f"(got d = {arch.dims[0]}, o = {arch.dims[-1]})")
+
+
+def check_gradloss_args(arch, dtype, xtrn, gtrn, lam):
+    """(N, o, d) float64 numpy gradient observations for `GradLoss` / loss_fn='gradloss'; refuses a missing or mis-shaped
+    `gtrn`, a negative `lam` and what `check_sobolev_args` refuses."""
+    check_sobolev_args(arch, dtype)
+    if gtrn is None:
+        raise ValueError("the gradient loss needs gtrn: the observed input gradients (N, d) or (N, o, d)")
+    if lam is None or not np.isfinite(float(lam)) or float(lam) < 0.0:
+        raise ValueError(f"the gradient loss needs a finite weight lam >= 0 (got {lam!r})")
+    d, o = arch.dims[0], arch.dims[-1]
+    n = np.asarray(xtrn).reshape(-1, d).shape[0]
+    g = np.asarray(gtrn.detach().cpu() if isinstance(gtrn, torch.Tensor) else gtrn, dtype=np.float64)
+    if g.shape not in ((n, o, d),) + (((n, d),) if o == 1 else ()):
+        raise ValueError(f"gtrn has shape {g.shape}; expected ({n}, {o}, {d})" + (f" or ({n}, {d})" if o == 1 else ""))
+    return g.reshape(n, o, d)
 
 
 def check_curvature_args(arch, dtype, kind):

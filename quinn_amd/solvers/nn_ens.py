@@ -35,7 +35,9 @@ class NN_Ens(QUiNNBase):
 
     def fit(self, xtrn, ytrn, **kwargs):
         """Train every member (keyword arguments as `nnfit`: val, lrate, batch_size, nepochs, wd,
-        optimizer, loss_fn, datanoise, lmbd, freq_out, ...; build-only: perm_mode)."""
+        optimizer, loss_fn, datanoise, lmbd, freq_out, ...; build-only: perm_mode).  loss_fn='gradloss' with gtrn (the
+        observed input gradients of xtrn, (N, d) or (N, o, d)) and lam trains every member on the reference's GradLoss,
+        each member's penalty over its own training rows."""
         ntrn = ytrn.shape[0]
         rows = np.stack([np.random.permutation(ntrn)[:int(ntrn * self.dfrac)] for _ in range(self.nens)])
         val = kwargs.pop('val', None)
@@ -73,14 +75,17 @@ class NN_Ens(QUiNNBase):
         jens = np.random.randint(0, self.nens)
         return self._predict_batch(self._best_w[jens:jens + 1], x)[0]
 
-    def _predict_ens_dev(self, x, nens=None):
+    def _ens_weights(self, nens=None):
         if nens is None:
             nens = self.nens
         if nens > self.nens:
             print(f"Warning: Requested {nens} but only {self.nens} ensemble members available.")
             nens = self.nens
         order = np.random.permutation(nens)
-        return self._predict_batch_dev(self._best_w[order], x)
+        return self._best_w[order]
+
+    def _predict_ens_dev(self, x, nens=None):
+        return self._predict_batch_dev(self._ens_weights(nens), x)
 
     def predict_ens(self, x, nens=None):
         """`(M,N,o)`: predictions of (a random permutation of) the members (nn_ens.py:85-110)."""

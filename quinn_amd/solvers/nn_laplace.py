@@ -193,8 +193,11 @@ class NN_Laplace(NN_RMS):
     def predict_sample(self, x):
         return self._predict_batch(self._draw_weights(1), x)[0]
 
+    def _ens_weights(self, nens=1):
+        return self._draw_weights(1 if nens is None else nens)
+
     def _predict_ens_dev(self, x, nens=1):
-        return self._predict_batch_dev(self._draw_weights(1 if nens is None else nens), x)
+        return self._predict_batch_dev(self._ens_weights(nens), x)
 
     def predict_ens(self, x, nens=1):
         """`(M,N,o)`: M draws of `predict_sample` (nn_laplace.py:141-154), evaluated as one batched forward."""

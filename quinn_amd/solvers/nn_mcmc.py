@@ -7,7 +7,8 @@ Mirror of the reference's `NN_MCMC` (quinn/solvers/nn_mcmc.py:15-200): same cons
 
 logpost(w) = -[ 0.5*SSE(w)/sigma^2 + (N/2) log 2pi + N log sigma ]   (no prior,
 nn_mcmc.py:64 -> losses.py:197-200); SSE and dSSE/dw come from the HIP kernels, the scalar
-tail is applied here in float64.
+tail is applied here in float64.  With gradient observations (`fit(..., gtrn=, gradnoise=)`) a second Gaussian
+likelihood term on the input Jacobian is added (host engine; `BatchedMLP.sobolev`).
 """
 import copy
 import sys
@@ -20,7 +21,7 @@ from ..mcmc.admcmc import AMCMC
 from ..mcmc.hmc import HMC
 from ..mcmc.mala import MALA
 from ..mcmc import diagnostics as diag
-from ..ops import BatchedMLP, neg_log_post_from_sse
+from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
 
@@ -56,14 +57,16 @@ class NN_MCMC(QUiNNBase):
     def _operator(self, lpinfo):
         # the cached operator belongs to these very objects (kept referenced here, compared with `is`: an id() alone
         # can be recycled by a new array after the old one is freed)
-        key = (lpinfo['xd'], lpinfo['yd'])
-        if self._op is None or self._op_key[0] is not key[0] or self._op_key[1] is not key[1]:
+        key = (lpinfo['xd'], lpinfo['yd'], lpinfo.get('gd'))
+        if self._op is None or any(a is not b for a, b in zip(self._op_key, key)):
             xd = np.asarray(lpinfo['xd'], dtype=np.float64)
             yd = np.asarray(lpinfo['yd'], dtype=np.float64)      # list of (o,) rows -> (N,o)
             self._op = BatchedMLP(self.arch, xd, yd.reshape(xd.shape[0], -1), device=self._device,
                                   dtype=self._dtype)
             if self.kernels == "float64":
                 self._op.use_exact_float64()
+            if key[2] is not None:
+                self._op.set_grad_data(key[2])
             self._op_key = key
         return self._op
 
@@ -78,6 +81,8 @@ class NN_MCMC(QUiNNBase):
         lpinfo = self.lpinfo if lpinfo is None else lpinfo
         self._check_ltype(lpinfo)
         op = self._operator(lpinfo)
+        if lpinfo.get('gd') is not None:
+            return self._logpost_grad_data(op, np.atleast_2d(W), lpinfo, False)[0]
         sse = op.sse(np.atleast_2d(W)).cpu().numpy()
         return -neg_log_post_from_sse(sse, len(lpinfo['yd']), lpinfo['lparams']['sigma'])
 
@@ -86,9 +91,23 @@ class NN_MCMC(QUiNNBase):
         lpinfo = self.lpinfo if lpinfo is None else lpinfo
         self._check_ltype(lpinfo)
         op = self._operator(lpinfo)
+        if lpinfo.get('gd') is not None:
+            return self._logpost_grad_data(op, np.atleast_2d(W), lpinfo, True)[1]
         _, g = op.sse_grad(np.atleast_2d(W))
         sig = np.float64(lpinfo['lparams']['sigma'])
         return -(0.5 * g.double().cpu().numpy() / sig ** 2)
+
+    @staticmethod
+    def _logpost_grad_data(op, W, lpinfo, want_grad):
+        """(log-posterior (C,), its gradient (C, p) or None) with gradient observations, one `sobolev` call:
+        -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2) - N o d (log sigma_g + log(2 pi) / 2)."""
+        sig, sg = np.float64(lpinfo['lparams']['sigma']), np.float64(lpinfo['lparams']['sigma_g'])
+        d, o = op.arch.dims[0], op.arch.dims[-1]
+        cv, cg = -0.5 / sig ** 2, -0.5 / sg ** 2
+        sse, gsse, g = op.sobolev(W, cv, cg, want_grad=want_grad)
+        half = 0.5 * np.log(2 * np.float64(np.pi))
+        lp = cv * sse.cpu().numpy() + cg * gsse.cpu().numpy() - op.N * o * (np.log(sig) + half) - op.N * o * d * (np.log(sg) + half)
+        return lp, (g.cpu().numpy() if want_grad else None)
 
     def logpost(self, modelpars, lpinfo):
         """float: log-posterior of one flat weight vector (reference signature)."""
@@ -101,7 +120,7 @@ class NN_MCMC(QUiNNBase):
     # -- fit -------------------------------------------------------------------------------
     def fit(self, xtrn, ytrn, zflag=True, datanoise=0.05, nmcmc=6000, param_ini=None, sampler='amcmc',
             sampler_params=None, *, nchains=1, seeds=None, engine='host', gather='all', gather_chain=None, bfgs_jac=None,
-            diagnostics=False, diag_nburn=None):
+            diagnostics=False, diag_nburn=None, gtrn=None, gradnoise=None):
         """Run MCMC over the flat weight vector.
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
@@ -133,6 +152,10 @@ class NN_MCMC(QUiNNBase):
             so it works with gather_chain='none'; host engines: the numpy chain is uploaded in bounded pieces.  Multi-rank:
             each rank reduces its own chains, the small per-chain statistics follow `gather`.  diag_nburn: rows discarded
             first (None: nmcmc // 2).  False (default): nothing is computed and `self.diagnostics` is None.
+            gtrn `(N, d)` | `(N, o, d)` with gradnoise (sigma_g): observed input gradients as a second Gaussian likelihood
+            term, log-posterior -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2)
+            - N o d (log sigma_g + log(2 pi) / 2) with gsse = sum (dM/dx - gtrn)^2; engine='host' only (the device engines'
+            accept kernels take a bare SSE).
         """
         self.diagnostics = None
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
@@ -140,6 +163,16 @@ class NN_MCMC(QUiNNBase):
         assert xtrn.shape[0] == ntrn_
         self.lpinfo = {'model': None, 'xd': xtrn, 'yd': [y for y in ytrn], 'ltype': 'classical',
                        'lparams': {'sigma': datanoise}}
+        if gtrn is not None:
+            if engine == 'device':
+                raise NotImplementedError("gradient observations (gtrn) need engine='host': the device samplers' accept "
+                                          "kernels take a bare sum of squared errors")
+            if gradnoise is None or not float(gradnoise) > 0.0:
+                raise ValueError("gtrn needs gradnoise > 0, the noise level of the gradient observations")
+            self.lpinfo['gd'] = check_gradloss_args(self.arch, self._dtype, xtrn, gtrn, 0.0)
+            self.lpinfo['lparams']['sigma_g'] = float(gradnoise)
+        elif gradnoise is not None:
+            raise ValueError("gradnoise goes with gtrn")
         if seeds is not None:
             seeds = list(seeds)
             nchains = len(seeds)
@@ -287,17 +320,21 @@ class NN_MCMC(QUiNNBase):
             cm = self.cmode[0 if chain is None else chain]
         return self.predict_sample(x, cm)
 
-    def _predict_ens_dev(self, x, nens=10, nburn=1000, chain=0):
+    def _ens_weights(self, nens=10, nburn=1000, chain=0):
+        nens = 10 if nens is None else nens
         if isinstance(chain, str):
             if chain != 'all':
                 raise ValueError("chain is an int or 'all'")
             samples = self.samples if self.samples.ndim == 3 else self.samples[None]
             picks = diag.pooled_rows(samples.shape[0], samples.shape[1], nens, nburn)
-            return self._predict_batch_dev(np.concatenate([samples[c][rows, :] for c, rows in picks]), x)
+            return np.concatenate([samples[c][rows, :] for c, rows in picks])
         samples = self.samples if self.samples.ndim == 2 else self.samples[chain]
         nevery = int((samples.shape[0] - nburn) / nens)
         rows = [nburn + j * nevery for j in range(nens)]
-        return self._predict_batch_dev(samples[rows, :], x)
+        return samples[rows, :]
+
+    def _predict_ens_dev(self, x, nens=10, nburn=1000, chain=0):
+        return self._predict_batch_dev(self._ens_weights(nens, nburn, chain), x)
 
     def predict_ens(self, x, nens=10, nburn=1000, chain=0):
         """`(M,N,o)`: predictions with M thinned post-burn-in samples, rows

@@ -164,8 +164,11 @@ class NN_SWAG(NN_Ens):
     def predict_sample(self, x):
         return self._predict_batch(self.sample_weights(1), x)[0]
 
+    def _ens_weights(self, nens=1):
+        return self.sample_weights(1 if nens is None else nens)
+
     def _predict_ens_dev(self, x, nens=1):
-        return self._predict_batch_dev(self.sample_weights(1 if nens is None else nens), x)
+        return self._predict_batch_dev(self._ens_weights(nens), x)
 
     def predict_ens(self, x, nens=1):
         """`(M,N,o)`: M draws of `predict_sample` (nn_swag.py:147-160), evaluated as one batched forward."""

@@ -104,6 +104,42 @@ class QUiNNBase():
             ycov, yvar = None, None
         return ymean, yvar, ycov
 
+    # -- input sensitivities dM/dx under the posterior (qn_mlp_input_jac) ---------------------------------
+    def _ens_weights(self, nens=None, **ens_args):
+        """The flat weight vectors `(M, p)` (numpy or device tensor) behind the solver's predictive ensemble, drawn exactly as
+        `predict_ens` draws them."""
+        raise NotImplementedError(f"{type(self).__name__} does not expose the weights of its predictive ensemble")
+
+    def _predict_jac_dev(self, x, nens=None, **ens_args):
+        W = self._ens_weights(nens, **ens_args)
+        x = np.asarray(x, dtype=np.float64)
+        if self._dtype != "float64":
+            raise ValueError(f"input sensitivities need the float64 operator (got dtype {self._dtype!r})")
+        if getattr(self, "_jac_op", None) is None:
+            self._jac_op = BatchedMLP(self.arch, x, None, device=self._device, dtype="float64")
+        return self._jac_op.input_jacobian(W, x)
+
+    def predict_jac_ens(self, x, nens=None, **ens_args):
+        """`(M, N, o, d)`: the input Jacobian d f_k(x_n) / d x_j of every member of the solver's predictive ensemble (the
+        members `predict_ens(x, nens, **ens_args)` evaluates), from one batched tangent forward."""
+        return self._predict_jac_dev(x, nens, **ens_args).cpu().numpy()
+
+    def predict_jac_mom_sample(self, x, msc=0, nsam=1000, **ens_args):
+        """Mean `(N, o, d)` and, with msc = 1, variance `(N, o, d)` (ddof=1; else None) of the input sensitivity over an
+        `nsam`-member posterior ensemble.  The Jacobians stay on the device; the moments come from `qn_pred_moments`."""
+        if msc not in (0, 1):
+            raise ValueError(f"msc={msc}, but needs to be 0 or 1")
+        J = self._predict_jac_dev(x, nsam, **ens_args).contiguous()
+        dev = J.device
+        M, K = J.shape[0], J[0].numel()
+        mean = torch.empty(J.shape[1:], dtype=torch.float64, device=dev)
+        var = torch.empty(J.shape[1:], dtype=torch.float64, device=dev) if msc == 1 else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().qn_pred_moments(J.data_ptr(), _lib.QN_F64, M, K, mean.data_ptr(),
+                                                  var.data_ptr() if var is not None else None,
+                                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qn_pred_moments")
+        return mean.cpu().numpy(), (var.cpu().numpy() if var is not None else None)
+
     # -- figures (presentation only; same signatures and file names as quinn.py:106-260) ---------------
     @staticmethod
     def _center_and_spread(yens, quantiles):
