@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|vi|ens|rms|laplace|laplace_ggn|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -10,6 +10,7 @@ once (`seeds=`), the MCMC branches pool their predictive ensemble over all chain
 and print how well the chains agree (split-R-hat / ESS of parameters, log-posterior and predictions),
 `laplace_ggn` is the Laplace solver with the Gauss-Newton curvature (`la_type='ggn'`, positive definite by construction) and
 prints its closed-form linearised predictive (`predict_glm`) beside the sampled one,
+`laplace_kron` is the same with the Kronecker-factored Gauss-Newton (`la_type='kron'`: two small factors per layer, no p x p matrix),
 and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
@@ -39,7 +40,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -48,7 +49,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn'):             # the Laplace curvature kernels take MLPs (RNet is not covered)
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron'):             # the Laplace curvature kernels take MLPs (RNet is not covered)
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -85,6 +86,10 @@ def main(meth, quick=False, mlp=False):
         uqnet = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='ggn', datanoise=datanoise)
         uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
         predict = lambda x: uqnet.predict_ens(x, nens=111)
+    elif meth == 'laplace_kron':
+        uqnet = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='kron', datanoise=datanoise)
+        uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
+        predict = lambda x: uqnet.predict_ens(x, nens=111)
     elif meth == 'swag':
         uqnet = NN_SWAG(nnet, nens=3, dfrac=1.0, verbose=not quick, k=10, n_steps=12, c=1, cov_type="lowrank",
                         lr_swag=0.01)
@@ -101,13 +106,13 @@ def main(meth, quick=False, mlp=False):
     print(f"{meth}: {y.shape[0]} predictive samples on an 11-point grid")
     for xg, m, s, t in zip(xgrid[:, 0], ymean, ystd, np.sin(xgrid[:, 0])):
         print(f"  x={xg:+.3f}  mean={m:+.4f}  std={s:.4f}  truth={t:+.4f}")
-    if meth == 'laplace_ggn':
+    if meth in ('laplace_ggn', 'laplace_kron'):
         gmean, gvar, _ = uqnet.predict_glm(xgrid, msc=1)
         print("  linearised (GLM) predictive in closed form beside the sampled one:")
         for xg, m, s, gm, gs in zip(xgrid[:, 0], ymean, ystd, gmean[:, 0], np.sqrt(gvar[:, 0])):
             print(f"  x={xg:+.3f}  sampled mean={m:+.4f} std={s:.4f}   glm mean={gm:+.4f} std={gs:.4f}")
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
-        if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
+        if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
     if meth in ('amcmc', 'hmc'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])

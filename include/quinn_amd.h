@@ -386,6 +386,42 @@ int qn_swag_step(int mode, double* W, const void* G, int gdtype, const double* l
 int qn_swag_sample(double* mean, const double* diag, const double* D, int K, const int32_t* js, const double* z1,
                    const double* z2, int M, int B, int64_t p, int drift, double* theta, void* stream);
 
+/* Kronecker-factored Gauss-Newton of an MLP ("kron" Laplace), float64.  With ~in_i = [in_i; 1] (length e_i = h_i + has_bias) the
+ * input of Linear layer i and g^k_i the backward signal at its output from output unit vector e_k, the factors are the SUMS
+ *   A_i = sum_n ~in_i ~in_i^T  [e_i, e_i],     S_i = sum_n sum_k g^k_i g^k_i^T  [h_{i+1}, h_{i+1}]
+ * over a member's rows; the layer-i diagonal block of sum_n sum_k J_nk^T J_nk is approximated by (S_i (x) A_i) / Nb, row index
+ * (unit a, input slot b), cross-layer blocks by zero (exact for Nb = 1, and for the last layer at every Nb).
+ * qn_kron_layout: offsets of the layers in a member's packed factors (offA, offS: arrays of nlayers entries, A_i at offA[i] of
+ *   lenA = sum e_i^2 doubles, S_i at offS[i] of lenS = sum h_{i+1}^2) and in KRON ORDER of a length-p vector: layer i, unit a,
+ *   slot c < e_i at offK[i] + a e_i + c -- not the flat parameter order when there are biases.  Any pointer may be NULL.
+ * qn_mlp_kron_factors: A_out [B, lenA], S_out [B, lenS]; the other arguments as for qn_mlp_curv (Y is not needed).  Symmetric
+ *   rank-k updates over row tiles on v_mfma_f64_16x16x4_f64; one triangle is computed and mirrored, so both triangles are written
+ *   and equal bit for bit.  Row-chunk partial sums in the workspace are added in a fixed order, no atomics: two calls give the
+ *   same bits and a member's result does not depend on B.
+ * qn_mlp_kron_glm_predict: the linearised predictive of qn_mlp_glm_predict for the posterior whose layer-i covariance is
+ *   (U_S (x) U_A) diag(Dinv_i) (U_S (x) U_A)^T.  UA [B, lenA], US [B, lenS]: the eigenvector matrices of the factors (eigenvectors
+ *   in the COLUMNS, row-major, packed like the factors); Dinv [B, p] in kron order: the variance of pair (a, c).
+ *     cov_out[b][n][k][l] = sum_i sum_{a,c} Dinv_i[a][c] gh^k_a gh^l_a ah_c^2,   gh^k = U_S^T g^k_i,  ah = U_A^T ~in_i at x_n
+ *   The rotations and the product (ah o ah) Dinv_i^T run on the f64 MFMA; the latter's accumulator tile is contracted with
+ *   gh^k o gh^l in the epilogue and never leaves the chip.  Entries (k, l) and (l, k) are one computed number; fixed summation
+ *   order, independent of B.  The workspace holds B x min(N, 1024) rows of layer inputs and backward signals, never N x p.
+ * qn_kron_sample: W_out [M, p] (flat order): draw m of member js[m] (int32 [M]) with the standard normals Z[m] ([M, p], flat
+ *   order): layer block = mean + U_S (Z_i o Dih_i) U_A^T, Z_i[a][b] the number at the flat position of parameter (i, a, b),
+ *   mean [B, p] flat, Dih [B, p] kron order (the standard deviation of pair (a, c)).  One launch for all M <= 65535 draws.
+ * Any MLP descriptor (tanh / relu / identity, with or without bias), layer widths up to 512, no limit on p.  A residual-network
+ * descriptor or a wider layer is QN_EINVAL with a message; the two workspace queries then return 0 (qn_last_error() says why).
+ * qn_kron_layout and the workspace queries need no device. */
+int qn_kron_layout(const qn_desc* desc, int64_t* offA, int64_t* offS, int64_t* offK, int64_t* lenA, int64_t* lenS);
+size_t qn_kron_workspace_bytes(const qn_desc* desc, int B, int Nb);
+int qn_mlp_kron_factors(const qn_desc* desc, const double* W, const double* X, const int32_t* row_idx, int B, int N, int Nb,
+                        double* A_out, double* S_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t qn_kron_glm_workspace_bytes(const qn_desc* desc, int B, int N);
+int qn_mlp_kron_glm_predict(const qn_desc* desc, const double* W, const double* X, const double* UA, const double* US,
+                            const double* Dinv, int B, int N, double* mean_out, double* cov_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int qn_kron_sample(const qn_desc* desc, const double* mean, const double* UA, const double* US, const double* Dih,
+                   const int32_t* js, const double* Z, double* W_out, int M, void* stream);
+
 /* Multi-chain MCMC diagnostics: the per-chain statistics from which split-R-hat, batch-means ESS and pooled moments follow
  * (quinn_amd/mcmc/diagnostics.py combines them; the reference runs one chain and has no counterpart).
  * chain [C, T, K] contiguous, dtype QN_F64 or QN_F32 (a stored chain, a log-posterior trace with K = 1, or the predictions

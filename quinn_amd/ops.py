@@ -492,6 +492,81 @@ class BatchedMLP:
                                                       ws.numel(), stream), "qn_mlp_glm_predict")
         return mean, cov
 
+    # ------------------------------------------------------------------ Kronecker-factored Gauss-Newton (qn_kron.hip)
+    def kron_layout(self):
+        """`KronLayout` of this network (qn_kron_layout; no device needed)."""
+        check_kron_args(self.arch, self.dtype)
+        if getattr(self, "_kron_lay", None) is None:
+            self._kron_lay = kron_layout(self.arch, self._L, self._desc)
+        return self._kron_lay
+
+    def kron_factors(self, W, row_idx=None):
+        """Kronecker factors of the Gauss-Newton matrix of every weight vector (qn_mlp_kron_factors): (A [B, lenA],
+        S [B, lenS], layout), float64 device tensors; `layout.A(A, i)` / `layout.S(S, i)` are the views [B, e_i, e_i] /
+        [B, h_{i+1}, h_{i+1}] of layer i.  A_i = sum_n ~in_i ~in_i^T and S_i = sum_n sum_k g^k_i g^k_i^T are SUMS over the member's
+        rows (`row_idx` [B, Nb]: member b sees rows row_idx[b] only), symmetric bit for bit; the layer block of the
+        Gauss-Newton matrix is approximated by (S_i (x) A_i) / Nb."""
+        lay = self.kron_layout()
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        ridx = self._row_idx(row_idx, B)
+        Nb = ridx.shape[1] if ridx is not None else self.N
+        A = torch.empty(B, lay.lenA, dtype=torch.float64, device=self.device)
+        S = torch.empty(B, lay.lenS, dtype=torch.float64, device=self.device)
+        if B == 0:
+            return A, S, lay
+        bc, nbytes = self._kron_chunk(self._L.qn_kron_workspace_bytes, "qn_kron_workspace_bytes", B, Nb)
+        ws = self._workspace(nbytes)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, bc):
+                b1 = min(B, b0 + bc)
+                _lib.check(self._L.qn_mlp_kron_factors(self._desc, Wt[b0:b1].data_ptr(), self.X.data_ptr(),
+                                                       ridx[b0:b1].data_ptr() if ridx is not None else None, b1 - b0, self.N,
+                                                       Nb, A[b0:b1].data_ptr(), S[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       stream), "qn_mlp_kron_factors")
+        return A, S, lay
+
+    def _kron_chunk(self, query, name, B, n):
+        """(members per call, workspace bytes): B halved until the workspace fits `max_workspace_bytes`."""
+        bc = min(B, 65535)
+        while True:
+            nbytes = int(query(self._desc, bc, n))
+            if nbytes == 0:
+                raise QuinnAmdError(f"{name}: {self._L.qn_last_error().decode()}")
+            if bc == 1 or nbytes <= self.max_ws:
+                return bc, nbytes
+            bc = (bc + 1) // 2
+
+    def kron_glm_predict(self, W, UA, US, Dinv, x=None):
+        """`glm_predict` for the Kronecker-factored posterior (qn_mlp_kron_glm_predict): (mean [B, N, o], cov [B, N, o, o]),
+        float64 device tensors.  UA [B, lenA], US [B, lenS]: the eigenvector matrices of the factors (eigenvectors in the
+        columns, as `torch.linalg.eigh` returns them), packed like the factors; Dinv [B, p] in kron order: the posterior
+        variance of the eigen-pair (a, c) of each layer.  No p x p array is formed; x defaults to the stored X."""
+        lay = self.kron_layout()
+        Wt = self.weights(W)
+        B = Wt.shape[0]
+        UA = _f64_rows(self._dev(UA, torch.float64), "UA", B, lay.lenA)
+        US = _f64_rows(self._dev(US, torch.float64), "US", B, lay.lenS)
+        Dinv = _f64_rows(self._dev(Dinv, torch.float64), "Dinv", B, self.p)
+        X = self.X if x is None else self._dev(x).reshape(-1, self.arch.dims[0])
+        N, o = X.shape[0], self.arch.dims[-1]
+        mean = torch.empty(B, N, o, dtype=torch.float64, device=self.device)
+        cov = torch.empty(B, N, o, o, dtype=torch.float64, device=self.device)
+        if B == 0 or N == 0:
+            return mean, cov
+        bc, nbytes = self._kron_chunk(self._L.qn_kron_glm_workspace_bytes, "qn_kron_glm_workspace_bytes", B, N)
+        ws = self._workspace(nbytes)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, bc):
+                b1 = min(B, b0 + bc)
+                _lib.check(self._L.qn_mlp_kron_glm_predict(self._desc, Wt[b0:b1].data_ptr(), X.data_ptr(), UA[b0:b1].data_ptr(),
+                                                           US[b0:b1].data_ptr(), Dinv[b0:b1].data_ptr(), b1 - b0, N,
+                                                           mean[b0:b1].data_ptr(), cov[b0:b1].data_ptr(), ws.data_ptr(),
+                                                           ws.numel(), stream), "qn_mlp_kron_glm_predict")
+        return mean, cov
+
     # ------------------------------------------------------------------ input derivatives (qn_sobolev.hip)
     def _sobolev_chunk(self, B, Nb, want_grad):
         """(members per call, workspace bytes): B halved until the workspace fits `max_workspace_bytes`, as `_chunk`."""
@@ -620,6 +695,71 @@ def check_curvature_args(arch, dtype, kind):
     return codes[kind]
 
 
+def check_kron_args(arch, dtype):
+    """Refuses what the Kronecker-factored kernels (qn_mlp_kron_factors / qn_mlp_kron_glm_predict / qn_kron_sample) do not take:
+    float32 (the factors are eigendecomposed and inverted, so they are float64 only) and residual networks."""
+    if dtype != "float64":
+        raise ValueError(f"the Kronecker-factored curvature needs the float64 operator (got dtype {dtype!r}): the factors are "
+                         "eigendecomposed and inverted")
+    if not isinstance(arch, MLPArch):
+        raise NotImplementedError("Kronecker-factored curvature of residual networks (RNet) is not supported; MLPs only")
+
+
+@dataclass(frozen=True)
+class KronLayout:
+    """Where layer i sits in a member's packed Kronecker factors and in kron order (qn_kron_layout): A_i [e_i, e_i] at offA[i]
+    of lenA doubles, S_i [h_{i+1}, h_{i+1}] at offS[i] of lenS, and (unit a, slot c) of a length-p vector at
+    offK[i] + a e_i + c.  `perm` (numpy int64 [p]) maps kron order to flat order: flat = perm[kron]."""
+    e: Tuple[int, ...]
+    h: Tuple[int, ...]
+    offA: Tuple[int, ...]
+    offS: Tuple[int, ...]
+    offK: Tuple[int, ...]
+    lenA: int
+    lenS: int
+    p: int
+    bias: bool
+
+    def A(self, t, i):
+        return t[..., self.offA[i]:self.offA[i] + self.e[i] ** 2].reshape(*t.shape[:-1], self.e[i], self.e[i])
+
+    def S(self, t, i):
+        return t[..., self.offS[i]:self.offS[i] + self.h[i] ** 2].reshape(*t.shape[:-1], self.h[i], self.h[i])
+
+    def K(self, t, i):
+        return t[..., self.offK[i]:self.offK[i] + self.h[i] * self.e[i]].reshape(*t.shape[:-1], self.h[i], self.e[i])
+
+    @property
+    def perm(self):
+        out = np.empty(self.p, dtype=np.int64)
+        for i, (e, h) in enumerate(zip(self.e, self.h)):
+            d = e - 1 if self.bias else e                      # input slots that carry weights; slot d is the bias
+            a, c = np.meshgrid(np.arange(h), np.arange(e), indexing="ij")
+            flat = np.where(c < d, self.offK[i] + a * d + c, self.offK[i] + h * d + a)
+            out[self.offK[i]:self.offK[i] + h * e] = flat.reshape(-1)
+        return out
+
+
+def kron_layout(arch, L=None, desc=None):
+    """`KronLayout` of an MLPArch from qn_kron_layout (needs the built library, no device)."""
+    L = L or _lib.lib()
+    own = desc is None
+    if own:
+        desc = arch.create_desc(L)
+    try:
+        n = len(arch.dims) - 1
+        arr = lambda: (ctypes.c_int64 * n)()                  # noqa: E731
+        oa, os_, ok = arr(), arr(), arr()
+        la, ls = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.qn_kron_layout(desc, oa, os_, ok, ctypes.byref(la), ctypes.byref(ls)), "qn_kron_layout")
+    finally:
+        if own:
+            L.qn_mlp_desc_destroy(desc)
+    hb = 1 if arch.bias else 0
+    return KronLayout(tuple(d + hb for d in arch.dims[:-1]), tuple(arch.dims[1:]), tuple(oa), tuple(os_), tuple(ok),
+                      int(la.value), int(ls.value), arch.nparams, bool(arch.bias))
+
+
 def neg_log_post_from_sse(sse, n, sigma):
     """0.5*SSE/sigma^2 + (n/2)*log(2*pi) + n*log(sigma) in float64 with the operation order
     of the reference's NegLogPost.forward (quinn/nns/losses.py:198-200); sse: float64 array."""
@@ -716,3 +856,47 @@ def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
         _lib.check(_lib.lib().qn_swag_sample(mean.data_ptr(), diag.data_ptr(), ptr(D), K, jsd.data_ptr(), z1d.data_ptr(),
                                              ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), st), "qn_swag_sample")
     return theta
+
+
+def kron_sample(arch, mean, UA, US, Dih, js, Z, out=None, op=None):
+    """`qn_kron_sample` on the current torch stream: W [M, p] float64 (device, flat order) of the M draws of the
+    Kronecker-factored posteriors: draw m uses member js[m] (host or device ints, each in [0, B)) and the standard normals
+    Z[m] ([M, p], flat order); per layer W = mean + U_S (Z o Dih) U_A^T.  mean [B, p] flat; UA [B, lenA], US [B, lenS]
+    eigenvector matrices packed like the factors; Dih [B, p] in kron order.  `op`: a float64 `BatchedMLP` of this architecture
+    whose descriptor and layout are reused (callers that draw repeatedly); without it a descriptor is made for the call."""
+    check_kron_args(arch, "float64")
+    B, p = _f64_rows(mean, "mean").shape
+    if p != arch.nparams:
+        raise ValueError(f"mean has {p} columns, the network has {arch.nparams} parameters")
+    dev = mean.device
+    L = _lib.lib()
+    if op is not None and (op.arch != arch or op.dtype != "float64"):
+        raise ValueError("op: a float64 BatchedMLP of the same architecture is needed")
+    desc = op._desc if op is not None else arch.create_desc(L)
+    try:
+        lay = op.kron_layout() if op is not None else kron_layout(arch, L, desc)
+        _f64_rows(UA, "UA", B, lay.lenA)
+        _f64_rows(US, "US", B, lay.lenS)
+        _f64_rows(Dih, "Dih", B, p)
+        js_h = np.asarray(js.cpu() if isinstance(js, torch.Tensor) else js).reshape(-1)
+        M = js_h.shape[0]
+        if M == 0:
+            return torch.empty(0, p, dtype=torch.float64, device=dev)
+        if js_h.min() < 0 or js_h.max() >= B:
+            raise ValueError(f"member indices must lie in [0, {B})")
+        jsd = torch.as_tensor(js_h.astype(np.int32), device=dev)
+        Zd = torch.as_tensor(Z, dtype=torch.float64, device=dev).reshape(M, p).contiguous()
+        if out is None:
+            out = torch.empty(M, p, dtype=torch.float64, device=dev)
+        _f64_rows(out, "out", M, p)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            for m0 in range(0, M, 65535):
+                m1 = min(M, m0 + 65535)
+                _lib.check(L.qn_kron_sample(desc, mean.data_ptr(), UA.data_ptr(), US.data_ptr(), Dih.data_ptr(),
+                                            jsd[m0:m1].data_ptr(), Zd[m0:m1].data_ptr(), out[m0:m1].data_ptr(), m1 - m0, st),
+                           "qn_kron_sample")
+    finally:
+        if op is None:
+            L.qn_mlp_desc_destroy(desc)
+    return out

@@ -16,6 +16,16 @@ Mirror of the reference's `NN_Laplace` (quinn/solvers/nn_laplace.py:11-154):
   3. Prediction: `jens = np.random.randint(0, nens)`, then `np.random.multivariate_normal(means[jens], cov_mats[jens])`.
      The draws are replayed in that order with a per-member SVD factor computed once (numpy's own recipe, so the samples
      equal numpy's bit for bit); the M weight vectors then go through ONE batched device forward.
+     'kron' (no counterpart in the reference): the Kronecker-factored Gauss-Newton.  Per Linear layer i two small matrices, the
+     sums A_i = sum_n ~in_i ~in_i^T and S_i = sum_n sum_k g^k_i g^k_i^T over the member's Nb rows (`qn_mlp_kron_factors`, one
+     call for all members); the layer block of G is approximated by (S_i (x) A_i) / Nb and cross-layer blocks by zero, so
+       H_i = (S_i (x) A_i) / (Nb datanoise^2) + I / priorsigma^2
+     is inverted EXACTLY through the two eigendecompositions (batched `torch.linalg.eigh` on the device; factor eigenvalues
+     below 0 are clamped to 0): the variance of eigen-pair (a, c) is 1 / (cov_scale (l_S,a l_A,c / (Nb datanoise^2) +
+     1 / priorsigma^2)).  No p x p array is formed -- the type for networks whose p is beyond 'ggn' (p > 16384).  Draws replay
+     `np.random.randint`, then `np.random.standard_normal(p)` per sample, and are formed by ONE `qn_kron_sample` call;
+     `predict_glm` goes through `qn_mlp_kron_glm_predict`.  `kron[j]` holds member j's factors, eigenbases and eigenvalues;
+     `dense_cov(j)` materialises the covariance in flat parameter order for small networks.
   4. `predict_glm`: the linearised ("GLM") predictive in closed form -- one `qn_mlp_glm_predict` call gives every member's
      mean f_b(x_n) and output covariance J Sigma_b J^T; the members' Gaussians are mixed with equal weights.  No draws, no SVD.
 """
@@ -24,7 +34,7 @@ import warnings
 import numpy as np
 import torch
 
-from ..ops import BatchedMLP
+from ..ops import BatchedMLP, check_kron_args, kron_sample
 from .nn_rms import NN_RMS
 
 LA_SIGMA = 0.1          # nn_laplace.py:107: NegLogPost(learner.nnmodel, ntrn, 0.1, None)
@@ -66,7 +76,7 @@ def glm_mixture(f, S, noise_var=0.0):
 
 
 class NN_Laplace(NN_RMS):
-    """Args: nnmodel, la_type ('full' | 'diag' | 'ggn' | 'ggn_diag'), cov_scale, datanoise (of the MAP fit), priorsigma, and the
+    """Args: nnmodel, la_type ('full' | 'diag' | 'ggn' | 'ggn_diag' | 'kron'), cov_scale, datanoise (of the MAP fit), priorsigma, and the
     `NN_Ens` keywords (nens, dfrac, verbose, device, dtype)."""
 
     def __init__(self, nnmodel, la_type='full', cov_scale=1.0, datanoise=0.1, priorsigma=1.0, **kwargs):
@@ -77,10 +87,13 @@ class NN_Laplace(NN_RMS):
         self.cov_mats = []
         self._factors = []
         self._cov_dev = []          # 'ggn': Sigma_j [p, p], 'ggn_diag': its diagonal [p], device float64 (None otherwise)
+        self.kron = []              # 'kron': per member a dict of per-layer device tensors (see `_store_kron`)
+        self._kron_packed = []      # 'kron': per member (UA [lenA], US [lenS], Dinv [p], Dih [p]) as the kernels take them
+        self._kron_stack = None     # the members' packed tensors and means stacked (built on first use)
 
     def _kind(self):
-        if self.la_type not in ('full', 'diag') + GGN_TYPES:
-            raise NotImplementedError(f"la_type {self.la_type!r}: only 'full', 'diag', 'ggn' and 'ggn_diag' are accepted")
+        if self.la_type not in ('full', 'diag', 'kron') + GGN_TYPES:
+            raise NotImplementedError(f"la_type {self.la_type!r}: only 'full', 'diag', 'ggn', 'ggn_diag' and 'kron' are accepted")
         return self.la_type
 
     def _store(self, w, hess):
@@ -118,6 +131,71 @@ class NN_Laplace(NN_RMS):
         self._cov_dev.append(cov)
         return H_np
 
+    def _store_kron(self, W, A, S, lay, nb):
+        """Members of type 'kron' from their factor sums A [B, lenA], S [B, lenS] (device) over nb rows each: batched
+        eigendecompositions per layer, then the variances Dinv and standard deviations Dih of the eigen-pairs.  `kron[j]` gets
+        nb, the layout and per-layer lists A, S (factors), UA, US (eigenvectors in the columns), lamA, lamS (eigenvalues,
+        clamped at 0), Dinv [h_{i+1}, e_i]."""
+        B = A.shape[0]
+        prior = 1.0 / self.priorsigma ** 2
+        scale = 1.0 / (nb * self.datanoise ** 2)
+        UA, US = torch.empty_like(A), torch.empty_like(S)
+        Dinv = torch.empty(B, lay.p, dtype=torch.float64, device=A.device)
+        per = [dict(nb=nb, layout=lay, A=[], S=[], UA=[], US=[], lamA=[], lamS=[], Dinv=[]) for _ in range(B)]
+        for i in range(len(lay.e)):
+            Ai, Si = lay.A(A, i), lay.S(S, i)
+            la_, ua = torch.linalg.eigh(Ai)
+            ls_, us = torch.linalg.eigh(Si)
+            la_, ls_ = la_.clamp_min(0.0), ls_.clamp_min(0.0)
+            lay.A(UA, i).copy_(ua)
+            lay.S(US, i).copy_(us)
+            di = 1.0 / (self.cov_scale * (ls_[:, :, None] * la_[:, None, :] * scale + prior))
+            lay.K(Dinv, i).copy_(di)
+            for b in range(B):
+                for key, v in (("A", Ai), ("S", Si), ("UA", ua), ("US", us), ("lamA", la_), ("lamS", ls_), ("Dinv", di)):
+                    per[b][key].append(v[b])
+        Dih = torch.sqrt(Dinv)
+        for b in range(B):
+            self.means.append(np.asarray(W[b], dtype=np.float64))
+            self.cov_mats.append(None)
+            self._factors.append(None)
+            self._cov_dev.append(None)
+            self.kron.append(per[b])
+            self._kron_packed.append((UA[b], US[b], Dinv[b], Dih[b]))
+        self._kron_stack = None
+
+    def _kron_dev(self):
+        """(means [B, p], UA, US, Dinv, Dih) of all members, stacked device tensors."""
+        if self._kron_stack is None:
+            dev = self._kron_packed[0][0].device
+            mean = torch.as_tensor(np.asarray(self.means), device=dev).contiguous()
+            self._kron_stack = (mean,) + tuple(torch.stack([m[q] for m in self._kron_packed]).contiguous() for q in range(4))
+        return self._kron_stack
+
+    def _kron_op(self, device):
+        """The operator whose descriptor and layout `kron_sample` reuses (no data rows needed)."""
+        if getattr(self, "_kron_sample_op", None) is None:
+            self._kron_sample_op = BatchedMLP(self.arch, np.zeros((1, self.arch.dims[0])), None, device=device)
+        return self._kron_sample_op
+
+    def dense_cov(self, j):
+        """Member j's covariance [p, p] in flat parameter order (numpy).  'kron': assembled from the eigen form, block by
+        block -- for tests and small networks, refused for p > 16384; the other types return `cov_mats[j]`."""
+        if self.la_type != 'kron':
+            return self.cov_mats[j]
+        k = self.kron[j]
+        lay = k["layout"]
+        if lay.p > 16384:
+            raise ValueError(f"dense_cov is refused for p = {lay.p} > 16384 parameters ({lay.p ** 2 * 8e-9:.1f} GB)")
+        cov = torch.zeros(lay.p, lay.p, dtype=torch.float64, device=k["UA"][0].device)
+        perm = torch.as_tensor(lay.perm, device=cov.device)
+        for i in range(len(lay.e)):
+            Q = torch.kron(k["US"][i].contiguous(), k["UA"][i].contiguous())          # row (a, b), column (a', c)
+            blk = (Q * k["Dinv"][i].reshape(-1)) @ Q.T
+            idx = perm[lay.offK[i]:lay.offK[i] + lay.h[i] * lay.e[i]]
+            cov[idx[:, None], idx[None, :]] = 0.5 * (blk + blk.T)
+        return cov.cpu().numpy()
+
     def _scaled(self, curv):
         """Reference scaling of the kernels' result (numpy, one member)."""
         if self.la_type == 'full':
@@ -127,10 +205,16 @@ class NN_Laplace(NN_RMS):
     def fit(self, xtrn, ytrn, **kwargs):
         """MAP fit of every member (`NN_RMS.fit`), then the curvature of all members in one batched call."""
         kind = self._kind()
+        if kind == 'kron':
+            check_kron_args(self.arch, self._dtype)
         super().fit(xtrn, ytrn, **kwargs)
         W = np.asarray(self.fit_results['final_w'], dtype=np.float64)
         op = BatchedMLP(self.arch, np.asarray(xtrn, dtype=np.float64), np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1),
                         device=self._device)
+        if kind == 'kron':
+            A, S, lay = op.kron_factors(W, row_idx=self.rows)
+            self._store_kron(W, A, S, lay, np.asarray(self.rows).reshape(len(W), -1).shape[1])
+            return
         if kind in GGN_TYPES:
             G = op.curvature(W, kind, row_idx=self.rows)
             self.hessians = [self._store_ggn(W[j], G[j]) for j in range(self.nens)]
@@ -150,6 +234,18 @@ class NN_Laplace(NN_RMS):
         ytrn = np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1)
         ntrn = len(xtrn)
         op = BatchedMLP(self.arch, xtrn, ytrn, device=self._device)
+        if kind == 'kron':                      # factor sums add over the batches; the single 1 / Nb uses the total row count
+            check_kron_args(self.arch, self._dtype)
+            if not batch_size:
+                A, S, lay = op.kron_factors(w[None])
+            else:
+                A = S = None
+                for i in range(0, ntrn, batch_size):
+                    rows = np.arange(i, min(ntrn, i + batch_size), dtype=np.int32)[None]
+                    a, s_, lay = op.kron_factors(w[None], row_idx=rows)
+                    A, S = (a, s_) if A is None else (A + a, S + s_)
+            self._store_kron(w[None], A, S, lay, ntrn)
+            return self.kron[-1]
         if kind in GGN_TYPES:                   # the prior enters once, after the per-batch Gauss-Newton sums
             if not batch_size:
                 G = op.curvature(w[None], kind)[0]
@@ -184,6 +280,13 @@ class NN_Laplace(NN_RMS):
 
     def _draw_weights(self, nens):
         """[M, p]: the reference's draws in its order (randint, then the member's multivariate normal) per sample."""
+        if self.la_type == 'kron':
+            js, Z = np.empty(nens, dtype=np.int32), np.empty((nens, self.nparams))
+            for s in range(nens):
+                js[s] = np.random.randint(0, self.nens)
+                Z[s] = np.random.standard_normal(self.nparams)
+            mean, UA, US, _, Dih = self._kron_dev()
+            return kron_sample(self.arch, mean, UA, US, Dih, js, Z, op=self._kron_op(mean.device))
         W = np.empty((nens, self.nparams))
         for s in range(nens):
             jens = np.random.randint(0, self.nens)
@@ -213,23 +316,28 @@ class NN_Laplace(NN_RMS):
         Returns (ymean (N,o), yvar (N,o) | None, ycov (N,o,o) | None); msc = 0 / 1 / 2 selects how much is returned.
         `ycov` is the covariance ACROSS THE OUTPUTS at each query point -- not `predict_mom_sample`'s (N,N,o), which is the
         covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal.
-        One `qn_mlp_glm_predict` call over all members; no weight draws and no SVD.  Works for every la_type; with 'full' the
-        covariance may not be positive semi-definite, and negative variances are reported (warned about, not clipped)."""
+        One `qn_mlp_glm_predict` call over all members ('kron': `qn_mlp_kron_glm_predict`, no p x p array); no weight draws and
+        no SVD.  Works for every la_type; with 'full' the covariance may not be positive semi-definite, and negative variances
+        are reported (warned about, not clipped)."""
         if msc not in (0, 1, 2):
             raise ValueError(f"msc={msc}, but needs to be 0, 1 or 2")
         if not self.means:
             raise RuntimeError("predict_glm needs a fitted solver (fit or la_calc)")
         x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
         op = BatchedMLP(self.arch, x, None, device=self._device)
-        diag = self.la_type in ('diag', 'ggn_diag')
-        sig = []
-        for j in range(len(self.means)):
-            c = self._cov_dev[j]
-            if c is None:
-                c = np.diag(self.cov_mats[j]) if diag else self.cov_mats[j]
-                c = torch.as_tensor(np.ascontiguousarray(c), device=op.device)
-            sig.append(c)
-        f, S = op.glm_predict(np.asarray(self.means), torch.stack(sig))
+        if self.la_type == 'kron':
+            mean, UA, US, Dinv, _ = self._kron_dev()
+            f, S = op.kron_glm_predict(mean, UA, US, Dinv)
+        else:
+            diag = self.la_type in ('diag', 'ggn_diag')
+            sig = []
+            for j in range(len(self.means)):
+                c = self._cov_dev[j]
+                if c is None:
+                    c = np.diag(self.cov_mats[j]) if diag else self.cov_mats[j]
+                    c = torch.as_tensor(np.ascontiguousarray(c), device=op.device)
+                sig.append(c)
+            f, S = op.glm_predict(np.asarray(self.means), torch.stack(sig))
         mean, cov = glm_mixture(f.cpu().numpy(), S.cpu().numpy(), self.datanoise ** 2 if noise else 0.0)
         var = np.stack([cov[:, k, k] for k in range(cov.shape[1])], axis=1)
         if np.any(var < 0):
