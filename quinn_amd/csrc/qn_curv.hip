@@ -30,6 +30,7 @@
 // order, members one after another: no atomics, two calls give the same bits.  Rows past the end of a tile are zero in every
 // per-row array (so they add exact zeros).
 #include "qn_curv_rows.h"
+#include "qn_host_args.h"
 
 namespace {
 
@@ -285,14 +286,7 @@ bool is_full(int kind) { return kind == QN_CURV_HESS_FULL || kind == QN_CURV_GGN
 bool is_ggn(int kind) { return kind == QN_CURV_GGN_FULL || kind == QN_CURV_GGN_DIAG; }
 
 bool fill_args(const qn_desc* d, int kind, int Nb, CurvArgs* g, const char* who) {
-    if (!d) {
-        qn_set_error("%s: NULL descriptor", who);
-        return false;
-    }
-    if (d->kind != QN_KIND_MLP) {
-        qn_set_error("%s: residual networks (RNet) are not supported; the curvature kernels take an MLP descriptor", who);
-        return false;
-    }
+    if (!qn_check_mlp_desc(d, who, "the curvature kernels")) return false;
     if (kind != QN_CURV_HESS_FULL && kind != QN_CURV_EF_DIAG && kind != QN_CURV_GGN_FULL && kind != QN_CURV_GGN_DIAG) {
         qn_set_error("%s: kind must be QN_CURV_HESS_FULL (0), QN_CURV_EF_DIAG (1), QN_CURV_GGN_FULL (2) or QN_CURV_GGN_DIAG (3), "
                      "got %d", who, kind);
@@ -326,15 +320,14 @@ struct CurvLayout { size_t in, gr, sp, s2, zg, ad, total; };
 
 CurvLayout layout(const CurvArgs& g, int kind) {
     CurvLayout l;
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += qn_align(doubles * sizeof(double)); return o; };
-    l.in = take((size_t)g.RT * g.EI);
-    l.gr = take((size_t)g.RT * g.D * (is_ggn(kind) ? g.o : 1));      // GGN: GK [o][RT][D]
-    l.sp = is_ggn(kind) ? 0 : take((size_t)g.RT * g.D);
-    l.s2 = is_ggn(kind) ? 0 : take((size_t)g.RT * g.D);
-    l.zg = kind == QN_CURV_HESS_FULL ? take((size_t)g.D * g.RT * g.D) : 0;
-    l.ad = kind == QN_CURV_HESS_FULL ? take((size_t)g.D * g.RT * g.D) : 0;
-    l.total = off;
+    qn_ws_carver c;
+    l.in = c.take_doubles((size_t)g.RT * g.EI);
+    l.gr = c.take_doubles((size_t)g.RT * g.D * (is_ggn(kind) ? g.o : 1));      // GGN: GK [o][RT][D]
+    l.sp = is_ggn(kind) ? 0 : c.take_doubles((size_t)g.RT * g.D);
+    l.s2 = is_ggn(kind) ? 0 : c.take_doubles((size_t)g.RT * g.D);
+    l.zg = kind == QN_CURV_HESS_FULL ? c.take_doubles((size_t)g.D * g.RT * g.D) : 0;
+    l.ad = kind == QN_CURV_HESS_FULL ? c.take_doubles((size_t)g.D * g.RT * g.D) : 0;
+    l.total = c.total;
     return l;
 }
 
@@ -355,23 +348,16 @@ extern "C" int qn_mlp_curv(const qn_desc* d, int kind, const double* W, const do
         qn_set_error("qn_mlp_curv: need B >= 1, N >= 1 and non-NULL W, X, Y (HESS_FULL / EF_DIAG), out");
         return QN_EINVAL;
     }
-    if (!row_idx && Nb != N) {
-        qn_set_error("qn_mlp_curv: without row_idx Nb (%d) must equal N (%d)", Nb, N);
-        return QN_EINVAL;
-    }
+    if (!qn_check_row_idx(row_idx, N, Nb, "qn_mlp_curv")) return QN_EINVAL;
     const CurvLayout l = layout(g, kind);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_curv: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_curv")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* IN = (double*)(ws + l.in);
-    double* G = (double*)(ws + l.gr);
-    double* SP = (double*)(ws + l.sp);
-    double* S2U = (double*)(ws + l.s2);
-    double* ZG = kind == QN_CURV_HESS_FULL ? (double*)(ws + l.zg) : nullptr;
-    double* AD = kind == QN_CURV_HESS_FULL ? (double*)(ws + l.ad) : nullptr;
+    double* IN = qn_ws_at(workspace, l.in);
+    double* G = qn_ws_at(workspace, l.gr);
+    double* SP = qn_ws_at(workspace, l.sp);
+    double* S2U = qn_ws_at(workspace, l.s2);
+    double* ZG = kind == QN_CURV_HESS_FULL ? qn_ws_at(workspace, l.zg) : nullptr;
+    double* AD = kind == QN_CURV_HESS_FULL ? qn_ws_at(workspace, l.ad) : nullptr;
     const int64_t P = g.p;
     const int ntiles = (Nb + g.RT - 1) / g.RT;
     for (int b = 0; b < B; ++b) {

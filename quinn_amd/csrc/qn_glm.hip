@@ -14,6 +14,7 @@
 // atomics, no dependence on the grid.  After the last column tile the lane copies cov[n][k][l] to cov[n][l][k].
 // COV_DIAG.  One wave per (n, k <= l): sum_P J_nk[P] sigma[P] J_nl[P], lanes strided over P, fixed butterfly.
 #include "qn_curv_rows.h"
+#include "qn_host_args.h"
 
 namespace {
 
@@ -179,14 +180,7 @@ __global__ __launch_bounds__(256) void k_glm_diag(CurvArgs g, const int2* __rest
 }
 
 bool glm_args(const qn_desc* d, int cov_kind, int B, int N, CurvArgs* g, const char* who) {
-    if (!d) {
-        qn_set_error("%s: NULL descriptor", who);
-        return false;
-    }
-    if (d->kind != QN_KIND_MLP) {
-        qn_set_error("%s: residual networks (RNet) are not supported; the linearised predictive takes an MLP descriptor", who);
-        return false;
-    }
+    if (!qn_check_mlp_desc(d, who, "the linearised predictive")) return false;
     if (cov_kind != QN_GLM_COV_FULL && cov_kind != QN_GLM_COV_DIAG) {
         qn_set_error("%s: cov_kind must be QN_GLM_COV_FULL (0) or QN_GLM_COV_DIAG (1), got %d", who, cov_kind);
         return false;
@@ -196,8 +190,9 @@ bool glm_args(const qn_desc* d, int cov_kind, int B, int N, CurvArgs* g, const c
                      who, (long long)d->p, GLM_MAX_P, (double)d->p * (double)d->p * 8e-9);
         return false;
     }
-    if (B <= 0 || B > 65535 || N <= 0) {
-        qn_set_error("%s: need 1 <= B <= 65535 members and N >= 1 query rows", who);
+    if (!qn_check_members(B, who)) return false;
+    if (N <= 0) {
+        qn_set_error("%s: need N >= 1 query rows", who);
         return false;
     }
     curv_fill_dims(d, g);
@@ -209,12 +204,11 @@ struct GlmLayout { size_t tab, in, gk, total; };
 
 GlmLayout glm_layout(const CurvArgs& g, int B) {
     GlmLayout l;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += qn_align(bytes); return o; };
-    l.tab = take((size_t)g.p * sizeof(int2));
-    l.in = take((size_t)B * g.RT * g.EI * sizeof(double));
-    l.gk = take((size_t)B * g.o * g.RT * g.D * sizeof(double));
-    l.total = off;
+    qn_ws_carver c;
+    l.tab = c.take((size_t)g.p * sizeof(int2));
+    l.in = c.take_doubles((size_t)B * g.RT * g.EI);
+    l.gk = c.take_doubles((size_t)B * g.o * g.RT * g.D);
+    l.total = c.total;
     return l;
 }
 
@@ -236,15 +230,11 @@ extern "C" int qn_mlp_glm_predict(const qn_desc* d, int cov_kind, const double* 
         return QN_EINVAL;
     }
     const GlmLayout l = glm_layout(g, B);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_glm_predict: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_glm_predict")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    int2* tab = (int2*)(ws + l.tab);
-    double* IN = (double*)(ws + l.in);
-    double* GK = (double*)(ws + l.gk);
+    int2* tab = qn_ws_at<int2>(workspace, l.tab);
+    double* IN = qn_ws_at(workspace, l.in);
+    double* GK = qn_ws_at(workspace, l.gk);
     hipLaunchKernelGGL(k_glm_table, dim3((unsigned)((g.p + 255) / 256)), dim3(256), 0, st, g, tab);
     QN_HIP_CHECK(hipGetLastError());
     const int npair = g.o * (g.o + 1) / 2;

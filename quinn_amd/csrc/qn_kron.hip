@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "qn_curv_rows.h"
+#include "qn_host_args.h"
 
 namespace {
 
@@ -325,14 +326,7 @@ __global__ __launch_bounds__(256) void k_kron_sample(CurvArgs g, KronArgs kr, co
 }
 
 bool kron_args(const qn_desc* d, CurvArgs* g, KronArgs* kr, const char* who) {
-    if (!d) {
-        qn_set_error("%s: NULL descriptor", who);
-        return false;
-    }
-    if (d->kind != QN_KIND_MLP) {
-        qn_set_error("%s: residual networks (RNet) are not supported; the Kronecker-factored kernels take an MLP descriptor", who);
-        return false;
-    }
+    if (!qn_check_mlp_desc(d, who, "the Kronecker-factored kernels")) return false;
     for (int i = 0; i <= d->nlayers; ++i)
         if (d->dims[i] > KRON_MAX_W) {
             qn_set_error("%s: layer width %d is not supported; the Kronecker-factored kernels take widths up to %d", who,
@@ -349,31 +343,30 @@ struct KronLayout { size_t in, gk, part, ah, gh, total; };
 
 KronLayout factor_layout(const CurvArgs& g, const KronArgs& kr, int B, int nchunks) {
     KronLayout l = {};
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += qn_align(doubles * sizeof(double)); return o; };
-    l.in = take((size_t)B * g.RT * g.EI);
-    l.gk = take((size_t)B * g.o * g.RT * g.D);
-    l.part = take((size_t)B * nchunks * (size_t)(kr.lenA + kr.lenS));
-    l.total = off;
+    qn_ws_carver c;
+    l.in = c.take_doubles((size_t)B * g.RT * g.EI);
+    l.gk = c.take_doubles((size_t)B * g.o * g.RT * g.D);
+    l.part = c.take_doubles((size_t)B * nchunks * (size_t)(kr.lenA + kr.lenS));
+    l.total = c.total;
     return l;
 }
 
 KronLayout glm_layout(const CurvArgs& g, int B) {
     KronLayout l = {};
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += qn_align(doubles * sizeof(double)); return o; };
-    l.in = take((size_t)B * g.RT * g.EI);
-    l.gk = take((size_t)B * g.o * g.RT * g.D);
-    l.ah = take((size_t)B * g.RT * g.EI);
-    l.gh = take((size_t)B * g.o * g.RT * g.D);
-    l.total = off;
+    qn_ws_carver c;
+    l.in = c.take_doubles((size_t)B * g.RT * g.EI);
+    l.gk = c.take_doubles((size_t)B * g.o * g.RT * g.D);
+    l.ah = c.take_doubles((size_t)B * g.RT * g.EI);
+    l.gh = c.take_doubles((size_t)B * g.o * g.RT * g.D);
+    l.total = c.total;
     return l;
 }
 
 bool factor_sizes(const qn_desc* d, int B, int Nb, CurvArgs* g, KronArgs* kr, int* nchunks, const char* who) {
     if (!kron_args(d, g, kr, who)) return false;
-    if (B <= 0 || B > 65535 || Nb <= 0) {
-        qn_set_error("%s: need 1 <= B <= 65535 members and Nb >= 1 rows", who);
+    if (!qn_check_members(B, who)) return false;
+    if (Nb <= 0) {
+        qn_set_error("%s: need Nb >= 1 rows", who);
         return false;
     }
     g->RT = std::min(KRON_RT, (Nb + 3) / 4 * 4);
@@ -383,8 +376,9 @@ bool factor_sizes(const qn_desc* d, int B, int Nb, CurvArgs* g, KronArgs* kr, in
 
 bool glm_sizes(const qn_desc* d, int B, int N, CurvArgs* g, KronArgs* kr, const char* who) {
     if (!kron_args(d, g, kr, who)) return false;
-    if (B <= 0 || B > 65535 || N <= 0) {
-        qn_set_error("%s: need 1 <= B <= 65535 members and N >= 1 query rows", who);
+    if (!qn_check_members(B, who)) return false;
+    if (N <= 0) {
+        qn_set_error("%s: need N >= 1 query rows", who);
         return false;
     }
     g->RT = std::min(KRON_GLM_RT, (N + 15) / 16 * 16);
@@ -426,20 +420,13 @@ extern "C" int qn_mlp_kron_factors(const qn_desc* d, const double* W, const doub
         qn_set_error("qn_mlp_kron_factors: need N >= 1 and non-NULL W, X, A_out, S_out");
         return QN_EINVAL;
     }
-    if (!row_idx && Nb != N) {
-        qn_set_error("qn_mlp_kron_factors: without row_idx Nb (%d) must equal N (%d)", Nb, N);
-        return QN_EINVAL;
-    }
+    if (!qn_check_row_idx(row_idx, N, Nb, "qn_mlp_kron_factors")) return QN_EINVAL;
     const KronLayout l = factor_layout(g, kr, B, nchunks);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_kron_factors: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_kron_factors")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* IN = (double*)(ws + l.in);
-    double* GK = (double*)(ws + l.gk);
-    double* part = (double*)(ws + l.part);
+    double* IN = qn_ws_at(workspace, l.in);
+    double* GK = qn_ws_at(workspace, l.gk);
+    double* part = qn_ws_at(workspace, l.part);
     const int nitems = kr.itemStart[2 * g.L];
     const int64_t len = kr.lenA + kr.lenS;
     for (int n0 = 0; n0 < Nb; n0 += g.RT) {
@@ -474,16 +461,12 @@ extern "C" int qn_mlp_kron_glm_predict(const qn_desc* d, const double* W, const 
         return QN_EINVAL;
     }
     const KronLayout l = glm_layout(g, B);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_kron_glm_predict: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_kron_glm_predict")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* IN = (double*)(ws + l.in);
-    double* GK = (double*)(ws + l.gk);
-    double* AH = (double*)(ws + l.ah);
-    double* GH = (double*)(ws + l.gh);
+    double* IN = qn_ws_at(workspace, l.in);
+    double* GK = qn_ws_at(workspace, l.gk);
+    double* AH = qn_ws_at(workspace, l.ah);
+    double* GH = qn_ws_at(workspace, l.gh);
     const size_t inStride = (size_t)g.RT * g.EI, gkStride = (size_t)g.o * g.RT * g.D;
     for (int n0 = 0; n0 < N; n0 += g.RT) {
         const int nrows = std::min(g.RT, N - n0);

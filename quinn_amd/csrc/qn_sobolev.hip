@@ -26,6 +26,7 @@
 // are added in chunk order, tiles in tile order, the two sums of squares block by block in a fixed order: no atomics, two
 // calls give the same bits, and nothing depends on B.
 #include "qn_curv_rows.h"
+#include "qn_host_args.h"
 #include <algorithm>
 
 namespace {
@@ -381,14 +382,7 @@ __global__ __launch_bounds__(256) void k_sob_reduce(const double* __restrict__ s
 struct SobLayout { size_t a, z0, z1, slab, part, total; int64_t strideA, strideZ; int ntiles, nblk; };
 
 bool fill_args(const qn_desc* d, int Nb, int want_grad, SobArgs* g, const char* who) {
-    if (!d) {
-        qn_set_error("%s: NULL descriptor", who);
-        return false;
-    }
-    if (d->kind != QN_KIND_MLP) {
-        qn_set_error("%s: residual networks (RNet) are not supported; the input-derivative kernels take an MLP descriptor", who);
-        return false;
-    }
+    if (!qn_check_mlp_desc(d, who, "the input-derivative kernels")) return false;
     const int din = d->dims[0], o = d->dims[d->nlayers];
     if (din > SOB_MAX_D || o > SOB_MAX_O) {
         qn_set_error("%s: d = %d inputs, o = %d outputs: the input-derivative kernels take d <= %d and o <= %d", who, din, o,
@@ -449,27 +443,23 @@ SobLayout layout(const SobArgs& g, int B, int Nb, int want_grad) {
     l.strideZ = (int64_t)g.RE * g.hmax;
     l.ntiles = (Nb + g.RT - 1) / g.RT;
     l.nblk = (g.RT + 255) / 256;
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += qn_align(doubles * sizeof(double)); return o; };
-    l.a = take((size_t)B * l.strideA);
-    l.z0 = take((size_t)B * l.strideZ);
-    l.z1 = want_grad ? take((size_t)B * l.strideZ) : 0;
-    l.slab = want_grad ? take((size_t)B * g.nchunks * g.p) : 0;
-    l.part = take((size_t)B * 2 * l.ntiles * l.nblk);
-    l.total = off;
+    qn_ws_carver c;
+    l.a = c.take_doubles((size_t)B * l.strideA);
+    l.z0 = c.take_doubles((size_t)B * l.strideZ);
+    l.z1 = want_grad ? c.take_doubles((size_t)B * l.strideZ) : 0;
+    l.slab = want_grad ? c.take_doubles((size_t)B * g.nchunks * g.p) : 0;
+    l.part = c.take_doubles((size_t)B * 2 * l.ntiles * l.nblk);
+    l.total = c.total;
     return l;
 }
 
 bool check_common(const char* who, const double* W, const double* X, const int32_t* row_idx, int B, int N, int Nb) {
-    if (B <= 0 || B > 65535 || N <= 0 || !W || !X) {
-        qn_set_error("%s: need 1 <= B <= 65535, N >= 1 and non-NULL W, X", who);
+    if (!qn_check_members(B, who)) return false;
+    if (N <= 0 || !W || !X) {
+        qn_set_error("%s: need N >= 1 and non-NULL W, X", who);
         return false;
     }
-    if (!row_idx && Nb != N) {
-        qn_set_error("%s: without row_idx Nb (%d) must equal N (%d)", who, Nb, N);
-        return false;
-    }
-    return true;
+    return qn_check_row_idx(row_idx, N, Nb, who);
 }
 
 // the forward of one row tile: leaves the last layer's Z in Z0 (and, for the reverse pass, every A_l)
@@ -515,14 +505,10 @@ extern "C" int qn_mlp_input_jac(const qn_desc* d, const double* W, const double*
         return QN_EINVAL;
     }
     const SobLayout l = layout(g, B, Nb, 0);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_input_jac: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_input_jac")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* A = (double*)(ws + l.a);
-    double* Z0 = (double*)(ws + l.z0);
+    double* A = qn_ws_at(workspace, l.a);
+    double* Z0 = qn_ws_at(workspace, l.z0);
     for (int tI = 0; tI < l.ntiles; ++tI) {
         const int n0 = tI * g.RT, nrows = std::min(g.RT, Nb - n0);
         const int rc = forward_tile(g, l, W, X, row_idx, B, Nb, n0, nrows, A, Z0, st);
@@ -551,17 +537,13 @@ extern "C" int qn_mlp_sobolev_fwdbwd(const qn_desc* d, const double* W, const do
         return QN_EINVAL;
     }
     const SobLayout l = layout(g, B, Nb, want_grad);
-    if (!workspace || workspace_bytes < l.total) {
-        qn_set_error("qn_mlp_sobolev_fwdbwd: workspace of %zu bytes, need %zu", workspace_bytes, l.total);
-        return QN_EWORKSPACE;
-    }
+    if (!qn_check_workspace(workspace, workspace_bytes, l.total, "qn_mlp_sobolev_fwdbwd")) return QN_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* A = (double*)(ws + l.a);
-    double* Z0 = (double*)(ws + l.z0);
-    double* Z1 = (double*)(ws + l.z1);
-    double* slab = (double*)(ws + l.slab);
-    double* part = (double*)(ws + l.part);
+    double* A = qn_ws_at(workspace, l.a);
+    double* Z0 = qn_ws_at(workspace, l.z0);
+    double* Z1 = qn_ws_at(workspace, l.z1);
+    double* slab = qn_ws_at(workspace, l.slab);
+    double* part = qn_ws_at(workspace, l.part);
     const int npart = l.ntiles * l.nblk;
     for (int tI = 0; tI < l.ntiles; ++tI) {
         const int n0 = tI * g.RT, nrows = std::min(g.RT, Nb - n0);

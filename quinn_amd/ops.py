@@ -19,6 +19,18 @@ _TORCH_DT = {"float64": torch.float64, "float32": torch.float32}
 _QN_DT = {"float64": _lib.QN_F64, "float32": _lib.QN_F32}
 
 
+def _ptr(t, rows=None):
+    """Device address of the tensor t (of its rows `rows`, a slice); None for None."""
+    if t is None:
+        return None
+    return (t if rows is None else t[rows]).data_ptr()
+
+
+def _stream(dev):
+    """The current torch stream of the device, as the C ABI takes it."""
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
 @dataclass(frozen=True)
 class MLPArch:
     """dims = (d, h_1, ..., h_L, o); flat layout [W_0, b_0, W_1, b_1, ...] with W row-major
@@ -323,11 +335,46 @@ class BatchedMLP:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _chunk(self, B, Nb, want_grad):
-        bc = min(B, 65535)                       # one chain per blockIdx.y / .z: the grid limit of the C ABI
-        while bc > 1 and self.workspace_bytes(bc, Nb, want_grad) > self.max_ws:
+    def _fit_chunk(self, B, query, name, zero_ok=False):
+        """(members per call, workspace bytes): min(B, 65535) members -- one per blockIdx.y / .z, the grid limit of the C
+        ABI -- halved until `query(bc)` bytes fit `max_workspace_bytes`.  A 0-byte answer is the refusal of the query `name`
+        unless `zero_ok`."""
+        bc = min(B, 65535)
+        while True:
+            nbytes = int(query(bc))
+            if nbytes == 0 and not zero_ok:
+                raise QuinnAmdError(f"{name}: {self._L.qn_last_error().decode()}")
+            if bc <= 1 or nbytes <= self.max_ws:
+                return bc, nbytes
             bc = (bc + 1) // 2
-        return bc
+
+    def _chunk(self, B, Nb, want_grad):
+        return self._fit_chunk(B, lambda bc: self.workspace_bytes(bc, Nb, want_grad), "qn_workspace_bytes", zero_ok=True)[0]
+
+    def _run_chunked(self, B, query, name, launch, zero_ok=False):
+        """The member-chunked call of every operator: `launch(m, nb, tail)` -- one C call and its `_lib.check` -- for every
+        slice m of nb members that `_fit_chunk` allows; `tail` = (workspace, its bytes, the current torch stream), the last
+        three arguments of the C entry points."""
+        bc, nbytes = self._fit_chunk(B, query, name, zero_ok)
+        ws = self._workspace(nbytes)
+        tail = (ws.data_ptr(), ws.numel(), _stream(self.device))
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, bc):
+                b1 = min(B, b0 + bc)
+                launch(slice(b0, b1), b1 - b0, tail)
+
+    def _row_idx(self, row_idx, B, N):
+        """(int32 device tensor [B, Nb] or None, Nb): member b sees the rows row_idx[b]; all N without `row_idx`."""
+        if row_idx is None:
+            return None, N
+        if not isinstance(row_idx, torch.Tensor):
+            row_idx = np.asarray(row_idx)
+        ridx = torch.as_tensor(row_idx, device=self.device).to(torch.int32).contiguous().reshape(B, -1)
+        return ridx, ridx.shape[1]
+
+    def _rows(self, x):
+        """The stored X, or the query points x as a [N, d] device tensor."""
+        return self.X if x is None else self._dev(x).reshape(-1, self.arch.dims[0])
 
     def weights(self, W):
         """[B, p] device tensor in the compute dtype (numpy float64 input is uploaded)."""
@@ -345,11 +392,7 @@ class BatchedMLP:
         N = X.shape[0]
         Wt = self.weights(W)
         B = Wt.shape[0]
-        if row_idx is not None:
-            ridx = torch.as_tensor(row_idx, device=self.device).to(torch.int32).contiguous().reshape(B, -1)
-            Nb = ridx.shape[1]
-        else:
-            ridx, Nb = None, N
+        ridx, Nb = self._row_idx(row_idx, B, N)
         o = self.arch.dims[-1]
         if out is not None:                          # caller-owned result buffers (engines that run inside a HIP graph)
             sse, grad = out
@@ -362,22 +405,14 @@ class BatchedMLP:
         pred = torch.empty(B, Nb, o, dtype=self.tdt, device=self.device) if want_pred else None
         if B == 0:                                   # nothing to evaluate (e.g. an empty shard of chains)
             return sse, pred, grad
-        bc = self._chunk(B, Nb, want_grad)
-        ws = self._workspace(self.workspace_bytes(bc, Nb, want_grad))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, bc):
-                b1 = min(B, b0 + bc)
-                nb = b1 - b0
-                args = [self._desc, self.qdt, Wt[b0:b1].data_ptr(), X.data_ptr(), Y.data_ptr(),
-                        ridx[b0:b1].data_ptr() if ridx is not None else None, nb, N, Nb,
-                        sse[b0:b1].data_ptr(), pred[b0:b1].data_ptr() if pred is not None else None]
-                if want_grad:
-                    rc = self._L.qn_mlp_sse_fwdbwd(*args, grad[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(), stream)
-                    _lib.check(rc, "qn_mlp_sse_fwdbwd")
-                else:
-                    rc = self._L.qn_mlp_sse_fwd(*args, ws.data_ptr(), ws.numel(), stream)
-                    _lib.check(rc, "qn_mlp_sse_fwd")
+        fn, what = (self._L.qn_mlp_sse_fwdbwd, "qn_mlp_sse_fwdbwd") if want_grad else (self._L.qn_mlp_sse_fwd, "qn_mlp_sse_fwd")
+
+        def launch(m, nb, tail):
+            outs = [_ptr(sse, m), _ptr(pred, m)] + ([_ptr(grad, m)] if want_grad else [])
+            _lib.check(fn(self._desc, self.qdt, _ptr(Wt, m), X.data_ptr(), Y.data_ptr(), _ptr(ridx, m), nb, N, Nb, *outs, *tail),
+                       what)
+        # a 0-byte workspace is an answer here (kernels that need none), not a refusal
+        self._run_chunked(B, lambda bc: self.workspace_bytes(bc, Nb, want_grad), "qn_workspace_bytes", launch, zero_ok=True)
         return sse, pred, grad
 
     def sse(self, W, row_idx=None):
@@ -396,11 +431,10 @@ class BatchedMLP:
             raise _lib.QuinnAmdError("qn_mlp_sse_parts failed")
         out = torch.empty(B, parts, dtype=torch.float64, device=self.device)
         ws = self._workspace(self.workspace_bytes(B, N, False))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
             _lib.check(self._L.qn_mlp_sse_fwd_parts(self._desc, self.qdt, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
-                                                    None, B, N, N, out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                       "qn_mlp_sse_fwd_parts")
+                                                    None, B, N, N, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    _stream(self.device)), "qn_mlp_sse_fwd_parts")
         return out
 
     def sse_grad(self, W, row_idx=None, out=None):
@@ -415,12 +449,9 @@ class BatchedMLP:
 
     def predict(self, W, x=None):
         """f_W(x) for every weight vector: [B, N, o] device tensor (x defaults to the stored X)."""
-        if x is None:
-            return self._call(W, None, True, False)[1]
-        X = self._dev(x).reshape(-1, self.arch.dims[0])
-        Y = torch.zeros(X.shape[0], self.arch.dims[-1], device=self.device, dtype=self.tdt)
+        X = self._rows(x)
+        Y = None if x is None else torch.zeros(X.shape[0], self.arch.dims[-1], device=self.device, dtype=self.tdt)
         return self._call(W, None, True, False, X=X, Y=Y)[1]
-
 
     # ------------------------------------------------------------------ curvature (Laplace approximation)
     def curvature(self, W, kind, row_idx=None):
@@ -428,15 +459,12 @@ class BatchedMLP:
         kind "full" -> [B, p, p] exact Hessian (symmetric bit for bit); "diag" -> [B, p] empirical-Fisher diagonal
         (1/Nb) sum_n (d/dW |r_n|^2 / 2)^2; "ggn" -> [B, p, p] generalised Gauss-Newton matrix sum_n sum_k J_nk^T J_nk
         (J_nk = d f_k(x_n) / dW; positive semi-definite, symmetric bit for bit); "ggn_diag" -> [B, p] its diagonal (a sum over
-        the rows, not a mean).  `row_idx` [B, Nb]: member b sees rows row_idx[b] only."""
+        the rows, not a mean).  `row_idx` [B, Nb]: member b sees rows row_idx[b] only.  All B members go in ONE call:
+        qn_mlp_curv loops over them on the host and its workspace does not depend on B."""
         code = check_curvature_args(self.arch, self.dtype, kind)
         Wt = self.weights(W)
         B = Wt.shape[0]
-        if row_idx is not None:
-            ridx = torch.as_tensor(np.asarray(row_idx), device=self.device).to(torch.int32).contiguous().reshape(B, -1)
-            Nb = ridx.shape[1]
-        else:
-            ridx, Nb = None, self.N
+        ridx, Nb = self._row_idx(row_idx, B, self.N)
         shape = (B, self.p, self.p) if code in (_lib.CURV_HESS_FULL, _lib.CURV_GGN_FULL) else (B, self.p)
         out = torch.empty(shape, dtype=torch.float64, device=self.device)
         if B == 0:
@@ -445,11 +473,10 @@ class BatchedMLP:
         if nbytes == 0:
             raise QuinnAmdError(f"qn_curv_workspace_bytes: {self._L.qn_last_error().decode()}")
         ws = self._workspace(nbytes)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.qn_mlp_curv(self._desc, code, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
-                                           ridx.data_ptr() if ridx is not None else None, B, self.N, Nb, out.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), stream), "qn_mlp_curv")
+            _lib.check(self._L.qn_mlp_curv(self._desc, code, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(), _ptr(ridx), B,
+                                           self.N, Nb, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)),
+                       "qn_mlp_curv")
         return out
 
     # ------------------------------------------------------------------ linearised predictive (qn_mlp_glm_predict)
@@ -468,28 +495,17 @@ class BatchedMLP:
             kind = _lib.GLM_COV_DIAG
         else:
             raise ValueError(f"Sigma has shape {tuple(Sg.shape)}; expected ({B}, {self.p}, {self.p}) or ({B}, {self.p})")
-        X = self.X if x is None else self._dev(x).reshape(-1, self.arch.dims[0])
+        X = self._rows(x)
         N, o = X.shape[0], self.arch.dims[-1]
         mean = torch.empty(B, N, o, dtype=torch.float64, device=self.device)
         cov = torch.empty(B, N, o, o, dtype=torch.float64, device=self.device)
         if B == 0 or N == 0:
             return mean, cov
-        bc = min(B, 65535)
-        while True:
-            nbytes = int(self._L.qn_glm_workspace_bytes(self._desc, kind, bc, N))
-            if nbytes == 0:
-                raise QuinnAmdError(f"qn_glm_workspace_bytes: {self._L.qn_last_error().decode()}")
-            if bc == 1 or nbytes <= self.max_ws:
-                break
-            bc = (bc + 1) // 2
-        ws = self._workspace(nbytes)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, bc):
-                b1 = min(B, b0 + bc)
-                _lib.check(self._L.qn_mlp_glm_predict(self._desc, kind, Wt[b0:b1].data_ptr(), X.data_ptr(), Sg[b0:b1].data_ptr(),
-                                                      b1 - b0, N, mean[b0:b1].data_ptr(), cov[b0:b1].data_ptr(), ws.data_ptr(),
-                                                      ws.numel(), stream), "qn_mlp_glm_predict")
+
+        def launch(m, nb, tail):
+            _lib.check(self._L.qn_mlp_glm_predict(self._desc, kind, _ptr(Wt, m), X.data_ptr(), _ptr(Sg, m), nb, N,
+                                                  _ptr(mean, m), _ptr(cov, m), *tail), "qn_mlp_glm_predict")
+        self._run_chunked(B, lambda bc: self._L.qn_glm_workspace_bytes(self._desc, kind, bc, N), "qn_glm_workspace_bytes", launch)
         return mean, cov
 
     # ------------------------------------------------------------------ Kronecker-factored Gauss-Newton (qn_kron.hip)
@@ -509,34 +525,17 @@ class BatchedMLP:
         lay = self.kron_layout()
         Wt = self.weights(W)
         B = Wt.shape[0]
-        ridx = self._row_idx(row_idx, B)
-        Nb = ridx.shape[1] if ridx is not None else self.N
+        ridx, Nb = self._row_idx(row_idx, B, self.N)
         A = torch.empty(B, lay.lenA, dtype=torch.float64, device=self.device)
         S = torch.empty(B, lay.lenS, dtype=torch.float64, device=self.device)
         if B == 0:
             return A, S, lay
-        bc, nbytes = self._kron_chunk(self._L.qn_kron_workspace_bytes, "qn_kron_workspace_bytes", B, Nb)
-        ws = self._workspace(nbytes)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, bc):
-                b1 = min(B, b0 + bc)
-                _lib.check(self._L.qn_mlp_kron_factors(self._desc, Wt[b0:b1].data_ptr(), self.X.data_ptr(),
-                                                       ridx[b0:b1].data_ptr() if ridx is not None else None, b1 - b0, self.N,
-                                                       Nb, A[b0:b1].data_ptr(), S[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       stream), "qn_mlp_kron_factors")
-        return A, S, lay
 
-    def _kron_chunk(self, query, name, B, n):
-        """(members per call, workspace bytes): B halved until the workspace fits `max_workspace_bytes`."""
-        bc = min(B, 65535)
-        while True:
-            nbytes = int(query(self._desc, bc, n))
-            if nbytes == 0:
-                raise QuinnAmdError(f"{name}: {self._L.qn_last_error().decode()}")
-            if bc == 1 or nbytes <= self.max_ws:
-                return bc, nbytes
-            bc = (bc + 1) // 2
+        def launch(m, nb, tail):
+            _lib.check(self._L.qn_mlp_kron_factors(self._desc, _ptr(Wt, m), self.X.data_ptr(), _ptr(ridx, m), nb, self.N, Nb,
+                                                   _ptr(A, m), _ptr(S, m), *tail), "qn_mlp_kron_factors")
+        self._run_chunked(B, lambda bc: self._L.qn_kron_workspace_bytes(self._desc, bc, Nb), "qn_kron_workspace_bytes", launch)
+        return A, S, lay
 
     def kron_glm_predict(self, W, UA, US, Dinv, x=None):
         """`glm_predict` for the Kronecker-factored posterior (qn_mlp_kron_glm_predict): (mean [B, N, o], cov [B, N, o, o]),
@@ -549,43 +548,22 @@ class BatchedMLP:
         UA = _f64_rows(self._dev(UA, torch.float64), "UA", B, lay.lenA)
         US = _f64_rows(self._dev(US, torch.float64), "US", B, lay.lenS)
         Dinv = _f64_rows(self._dev(Dinv, torch.float64), "Dinv", B, self.p)
-        X = self.X if x is None else self._dev(x).reshape(-1, self.arch.dims[0])
+        X = self._rows(x)
         N, o = X.shape[0], self.arch.dims[-1]
         mean = torch.empty(B, N, o, dtype=torch.float64, device=self.device)
         cov = torch.empty(B, N, o, o, dtype=torch.float64, device=self.device)
         if B == 0 or N == 0:
             return mean, cov
-        bc, nbytes = self._kron_chunk(self._L.qn_kron_glm_workspace_bytes, "qn_kron_glm_workspace_bytes", B, N)
-        ws = self._workspace(nbytes)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, bc):
-                b1 = min(B, b0 + bc)
-                _lib.check(self._L.qn_mlp_kron_glm_predict(self._desc, Wt[b0:b1].data_ptr(), X.data_ptr(), UA[b0:b1].data_ptr(),
-                                                           US[b0:b1].data_ptr(), Dinv[b0:b1].data_ptr(), b1 - b0, N,
-                                                           mean[b0:b1].data_ptr(), cov[b0:b1].data_ptr(), ws.data_ptr(),
-                                                           ws.numel(), stream), "qn_mlp_kron_glm_predict")
+
+        def launch(m, nb, tail):
+            _lib.check(self._L.qn_mlp_kron_glm_predict(self._desc, _ptr(Wt, m), X.data_ptr(), _ptr(UA, m), _ptr(US, m),
+                                                       _ptr(Dinv, m), nb, N, _ptr(mean, m), _ptr(cov, m), *tail),
+                       "qn_mlp_kron_glm_predict")
+        self._run_chunked(B, lambda bc: self._L.qn_kron_glm_workspace_bytes(self._desc, bc, N), "qn_kron_glm_workspace_bytes",
+                          launch)
         return mean, cov
 
     # ------------------------------------------------------------------ input derivatives (qn_sobolev.hip)
-    def _sobolev_chunk(self, B, Nb, want_grad):
-        """(members per call, workspace bytes): B halved until the workspace fits `max_workspace_bytes`, as `_chunk`."""
-        bc = min(B, 65535)
-        while True:
-            nbytes = int(self._L.qn_sobolev_workspace_bytes(self._desc, bc, Nb, int(want_grad)))
-            if nbytes == 0:
-                raise QuinnAmdError(f"qn_sobolev_workspace_bytes: {self._L.qn_last_error().decode()}")
-            if bc == 1 or nbytes <= self.max_ws:
-                return bc, nbytes
-            bc = (bc + 1) // 2
-
-    def _row_idx(self, row_idx, B):
-        if row_idx is None:
-            return None
-        if not isinstance(row_idx, torch.Tensor):
-            row_idx = np.asarray(row_idx)
-        return torch.as_tensor(row_idx, device=self.device).to(torch.int32).contiguous().reshape(B, -1)
-
     def input_jacobian(self, W, x=None, want_pred=False):
         """d f_k(x_n) / d x_j at every weight vector: float64 device tensor [B, N, o, d] (qn_mlp_input_jac); with
         `want_pred` the pair (jacobian, predictions [B, N, o]) from the same pass.  x defaults to the stored X.  B is chunked
@@ -594,21 +572,17 @@ class BatchedMLP:
         Wt = self.weights(W)
         B = Wt.shape[0]
         d, o = self.arch.dims[0], self.arch.dims[-1]
-        X = self.X if x is None else self._dev(x).reshape(-1, d)
+        X = self._rows(x)
         N = X.shape[0]
         jac = torch.empty(B, N, o, d, dtype=torch.float64, device=self.device)
         pred = torch.empty(B, N, o, dtype=torch.float64, device=self.device) if want_pred else None
+
+        def launch(m, nb, tail):
+            _lib.check(self._L.qn_mlp_input_jac(self._desc, _ptr(Wt, m), X.data_ptr(), None, nb, N, N, _ptr(pred, m),
+                                                _ptr(jac, m), *tail), "qn_mlp_input_jac")
         if B > 0 and N > 0:
-            bc, nbytes = self._sobolev_chunk(B, N, False)
-            ws = self._workspace(nbytes)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            with torch.cuda.device(self.device):
-                for b0 in range(0, B, bc):
-                    b1 = min(B, b0 + bc)
-                    _lib.check(self._L.qn_mlp_input_jac(self._desc, Wt[b0:b1].data_ptr(), X.data_ptr(), None, b1 - b0, N, N,
-                                                        pred[b0:b1].data_ptr() if pred is not None else None,
-                                                        jac[b0:b1].data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                               "qn_mlp_input_jac")
+            self._run_chunked(B, lambda bc: self._L.qn_sobolev_workspace_bytes(self._desc, bc, N, 0),
+                              "qn_sobolev_workspace_bytes", launch)
         return (jac, pred) if want_pred else jac
 
     def set_grad_data(self, g):
@@ -630,37 +604,37 @@ class BatchedMLP:
             raise ValueError("sobolev: no gradient observations for the stored rows; call set_grad_data(g) first")
         Wt = self.weights(W)
         B = Wt.shape[0]
-        ridx = self._row_idx(row_idx, B)
-        Nb = ridx.shape[1] if ridx is not None else self.N
+        ridx, Nb = self._row_idx(row_idx, B, self.N)
         sse = torch.empty(B, dtype=torch.float64, device=self.device)
         gsse = torch.empty(B, dtype=torch.float64, device=self.device)
         grad = torch.empty(B, self.p, dtype=torch.float64, device=self.device) if want_grad else None
         if B == 0:
             return sse, gsse, grad
-        bc, nbytes = self._sobolev_chunk(B, Nb, want_grad)
-        ws = self._workspace(nbytes)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, bc):
-                b1 = min(B, b0 + bc)
-                _lib.check(self._L.qn_mlp_sobolev_fwdbwd(
-                    self._desc, Wt[b0:b1].data_ptr(), self.X.data_ptr(), self.Y.data_ptr(), self.G.data_ptr(),
-                    ridx[b0:b1].data_ptr() if ridx is not None else None, b1 - b0, self.N, Nb, float(wv), float(wg),
-                    sse[b0:b1].data_ptr(), gsse[b0:b1].data_ptr(), grad[b0:b1].data_ptr() if want_grad else None,
-                    ws.data_ptr(), ws.numel(), stream), "qn_mlp_sobolev_fwdbwd")
+
+        def launch(m, nb, tail):
+            _lib.check(self._L.qn_mlp_sobolev_fwdbwd(
+                self._desc, _ptr(Wt, m), self.X.data_ptr(), self.Y.data_ptr(), self.G.data_ptr(), _ptr(ridx, m), nb, self.N,
+                Nb, float(wv), float(wg), _ptr(sse, m), _ptr(gsse, m), _ptr(grad, m), *tail), "qn_mlp_sobolev_fwdbwd")
+        self._run_chunked(B, lambda bc: self._L.qn_sobolev_workspace_bytes(self._desc, bc, Nb, int(want_grad)),
+                          "qn_sobolev_workspace_bytes", launch)
         return sse, gsse, grad
 
 
 SOBOLEV_MAX_D = SOBOLEV_MAX_O = 16
 
 
+def _check_f64_mlp(arch, dtype, what, why=""):
+    """The refusals every float64 extension operator shares: float32 (ValueError) and residual networks (NotImplementedError)."""
+    if dtype != "float64":
+        raise ValueError(f"{what}: the float64 operator is needed (got dtype {dtype!r}){why}")
+    if not isinstance(arch, MLPArch):
+        raise NotImplementedError(f"{what}: residual networks (RNet) are not supported; MLPs only")
+
+
 def check_sobolev_args(arch, dtype):
     """Refuses what the input-derivative kernels (qn_mlp_input_jac / qn_mlp_sobolev_fwdbwd) do not take: float32 (they are
     float64 only), residual networks, more than 16 inputs or outputs."""
-    if dtype != "float64":
-        raise ValueError(f"input derivatives need the float64 operator (got dtype {dtype!r})")
-    if not isinstance(arch, MLPArch):
-        raise NotImplementedError("input derivatives of residual networks (RNet) are not supported; MLPs only")
+    _check_f64_mlp(arch, dtype, "input derivatives")
     if arch.dims[0] > SOBOLEV_MAX_D or arch.dims[-1] > SOBOLEV_MAX_O:
         raise NotImplementedError(f"input derivatives take d <= {SOBOLEV_MAX_D} inputs and o <= {SOBOLEV_MAX_O} outputs "
                                   f"(got d = {arch.dims[0]}, o = {arch.dims[-1]})")
@@ -688,21 +662,14 @@ def check_curvature_args(arch, dtype, kind):
     codes = {"full": _lib.CURV_HESS_FULL, "diag": _lib.CURV_EF_DIAG, "ggn": _lib.CURV_GGN_FULL, "ggn_diag": _lib.CURV_GGN_DIAG}
     if kind not in codes:
         raise ValueError(f"curvature kind {kind!r}: 'full', 'diag', 'ggn' or 'ggn_diag'")
-    if dtype != "float64":
-        raise ValueError(f"curvature needs the float64 operator (got dtype {dtype!r}): the Hessian is inverted")
-    if not isinstance(arch, MLPArch):
-        raise NotImplementedError("curvature of residual networks (RNet) is not supported; MLPs only")
+    _check_f64_mlp(arch, dtype, "curvature", ": the Hessian is inverted")
     return codes[kind]
 
 
 def check_kron_args(arch, dtype):
     """Refuses what the Kronecker-factored kernels (qn_mlp_kron_factors / qn_mlp_kron_glm_predict / qn_kron_sample) do not take:
     float32 (the factors are eigendecomposed and inverted, so they are float64 only) and residual networks."""
-    if dtype != "float64":
-        raise ValueError(f"the Kronecker-factored curvature needs the float64 operator (got dtype {dtype!r}): the factors are "
-                         "eigendecomposed and inverted")
-    if not isinstance(arch, MLPArch):
-        raise NotImplementedError("Kronecker-factored curvature of residual networks (RNet) is not supported; MLPs only")
+    _check_f64_mlp(arch, dtype, "Kronecker-factored curvature", ": the factors are eigendecomposed and inverted")
 
 
 @dataclass(frozen=True)
@@ -800,6 +767,15 @@ def _f64_rows(t, name, B=None, p=None):
     return t
 
 
+def _draw_members(js, B, dev):
+    """(int32 device tensor [M], M) of the draws' member indices js (host or device ints), each checked on the host to lie in
+    [0, B)."""
+    js_h = np.asarray(js.cpu() if isinstance(js, torch.Tensor) else js).reshape(-1)
+    if js_h.size and (js_h.min() < 0 or js_h.max() >= B):
+        raise ValueError(f"member indices must lie in [0, {B})")
+    return torch.as_tensor(js_h.astype(np.int32), device=dev), js_h.shape[0]
+
+
 def swag_step(mode, W, G=None, lr=None, gscale=1.0, m1=None, m2=None, D=None, slot=0, n=0):
     """One `qn_swag_step` pass on the current torch stream.  W, m1, m2: [B, p] float64 device tensors (updated in place);
     G: [B, p] float64 or float32; lr: [B] float64; D: [B, K, p] float64 ring buffer or None.  mode: `_lib.SWAG_INIT`
@@ -819,12 +795,9 @@ def swag_step(mode, W, G=None, lr=None, gscale=1.0, m1=None, m2=None, D=None, sl
     if D is not None:
         _f64_rows(D, "D", B, p)
         K = D.shape[1]
-    L = _lib.lib()
-    ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-    st = ctypes.c_void_p(torch.cuda.current_stream(W.device).cuda_stream)
     with torch.cuda.device(W.device):
-        _lib.check(L.qn_swag_step(int(mode), ptr(W), ptr(G), gdt, ptr(lr), float(gscale), ptr(m1), ptr(m2), ptr(D), K,
-                                  int(slot), int(n), B, p, st), "qn_swag_step")
+        _lib.check(_lib.lib().qn_swag_step(int(mode), _ptr(W), _ptr(G), gdt, _ptr(lr), float(gscale), _ptr(m1), _ptr(m2), _ptr(D),
+                                           K, int(slot), int(n), B, p, _stream(W.device)), "qn_swag_step")
 
 
 def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
@@ -834,13 +807,9 @@ def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
     B, p = _f64_rows(mean, "mean").shape
     _f64_rows(diag, "diag", B, p)
     dev = mean.device
-    js_h = np.asarray(js.cpu() if isinstance(js, torch.Tensor) else js).reshape(-1)
-    M = js_h.shape[0]
+    jsd, M = _draw_members(js, B, dev)
     if M == 0:
         return torch.empty(0, p, dtype=torch.float64, device=dev)
-    if js_h.min() < 0 or js_h.max() >= B:
-        raise ValueError(f"member indices must lie in [0, {B})")
-    jsd = torch.as_tensor(js_h.astype(np.int32), device=dev)
     z1d = _f64_rows(torch.as_tensor(z1, dtype=torch.float64, device=dev).reshape(M, p).contiguous(), "z1", M, p)
     K, z2d = 0, None
     if D is not None:
@@ -850,11 +819,10 @@ def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
     if theta is None:
         theta = torch.empty(M, p, dtype=torch.float64, device=dev)
     _f64_rows(theta, "theta", M, p)
-    ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().qn_swag_sample(mean.data_ptr(), diag.data_ptr(), ptr(D), K, jsd.data_ptr(), z1d.data_ptr(),
-                                             ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), st), "qn_swag_sample")
+        _lib.check(_lib.lib().qn_swag_sample(mean.data_ptr(), diag.data_ptr(), _ptr(D), K, jsd.data_ptr(), z1d.data_ptr(),
+                                             _ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), _stream(dev)),
+                   "qn_swag_sample")
     return theta
 
 
@@ -878,20 +846,16 @@ def kron_sample(arch, mean, UA, US, Dih, js, Z, out=None, op=None):
         _f64_rows(UA, "UA", B, lay.lenA)
         _f64_rows(US, "US", B, lay.lenS)
         _f64_rows(Dih, "Dih", B, p)
-        js_h = np.asarray(js.cpu() if isinstance(js, torch.Tensor) else js).reshape(-1)
-        M = js_h.shape[0]
+        jsd, M = _draw_members(js, B, dev)
         if M == 0:
             return torch.empty(0, p, dtype=torch.float64, device=dev)
-        if js_h.min() < 0 or js_h.max() >= B:
-            raise ValueError(f"member indices must lie in [0, {B})")
-        jsd = torch.as_tensor(js_h.astype(np.int32), device=dev)
         Zd = torch.as_tensor(Z, dtype=torch.float64, device=dev).reshape(M, p).contiguous()
         if out is None:
             out = torch.empty(M, p, dtype=torch.float64, device=dev)
         _f64_rows(out, "out", M, p)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _stream(dev)
         with torch.cuda.device(dev):
-            for m0 in range(0, M, 65535):
+            for m0 in range(0, M, 65535):                         # draws, one per blockIdx.y: no workspace, nothing to fit
                 m1 = min(M, m0 + 65535)
                 _lib.check(L.qn_kron_sample(desc, mean.data_ptr(), UA.data_ptr(), US.data_ptr(), Dih.data_ptr(),
                                             jsd[m0:m1].data_ptr(), Zd[m0:m1].data_ptr(), out[m0:m1].data_ptr(), m1 - m0, st),

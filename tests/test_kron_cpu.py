@@ -2,6 +2,8 @@
 covariance, linearised predictive, sampler -- against torch.func Jacobians; the layout / workspace queries and refusals of the new
 entry points (no device needed) and the argument checks of the 'kron' Laplace type."""
 import ctypes
+import json
+import os
 
 import numpy as np
 import pytest
@@ -228,3 +230,24 @@ def test_kron_argument_checks():
     assert NN_Laplace(net, la_type="kron", nens=1)._kind() == "kron"
     with pytest.raises(NotImplementedError):
         NN_Laplace(net, la_type="kfac", nens=1)._kind()
+
+
+def test_extension_workspace_sizes_unchanged(L):
+    """Every workspace-size query of the float64 extension operators (curvature, linearised predictive, Kronecker factors and
+    predictive, input derivatives) returns what tests/golden/g16_ext_workspace_bytes.json records: the numbers of the library
+    before the host plumbing of these operators was shared (gen_golden_ws_sizes.py), so the workspace layouts are unchanged."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g16_ext_workspace_bytes.json")) as f:
+        cases = json.load(f)
+    queries = {c["query"] for c in cases}
+    assert queries == {"qn_curv_workspace_bytes", "qn_glm_workspace_bytes", "qn_kron_workspace_bytes",
+                       "qn_kron_glm_workspace_bytes", "qn_sobolev_workspace_bytes"} and len(cases) == 180
+    descs = {}
+    for c in cases:
+        key = (tuple(c["dims"]), c["act"], c["bias"])
+        if key not in descs:
+            descs[key] = _desc(L, key[0], _lib.ACT_CODES[key[1]], key[2])
+        assert c["bytes"] > 0
+        assert getattr(L, c["query"])(descs[key], *c["args"]) == c["bytes"], c
+    assert len(descs) == 3 and any(k[2] == 0 for k in descs)
+    for h in descs.values():
+        L.qn_mlp_desc_destroy(h)
