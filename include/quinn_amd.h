@@ -292,6 +292,37 @@ int qn_hmc_accept(const double* q, const double* grad_q, const double* sse_q, co
                   uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best, double* best_lp,
                   double* chain, double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr, int parity, void* stream);
 
+/* Device HMC / MALA with a per-chain step size eps [C] and a diagonal mass matrix, both DEVICE arrays, and their warm-up.
+ * scale [C, p] > 0 is the square root of the inverse mass, M^-1 = diag(scale^2); NULL means 1.  The leapfrog runs in whitened
+ * momenta u = scale * r (r the momentum), so u ~ N(0, I), the kinetic energy is |u|^2 / 2 and qn_hmc_accept is used unchanged:
+ *     z ~ N(0, I);  u = z + (eps_c/2) s * g(cur);  q = cur + eps_c s * u
+ *     L-1 times:    u += eps_c s * g(q);  q += eps_c s * u
+ *     last:         u += (eps_c/2) s * g(q);          K_cur = sum z^2 / 2,  K_prop = sum u^2 / 2        (g = d logpost / d W)
+ * qn_hmc_begin_s / qn_hmc_leap_s: qn_hmc_begin / qn_hmc_leap with the per-element factors (kick_c * s) and (eps_c * s) in
+ *   place of the scalars -- same grid (qn_hmc_parts(p) workgroups per chain), same Philox keys (seed, 2 * step, global chain
+ *   id), same fixed-order partial sums: with scale NULL or 1 and equal eps_c they give those calls' results bit for bit.
+ * qn_hmc_adapt: one launch per warm-up step, after the accept call of that step.  Per chain it reads the step t just decided
+ *   from slot `parity` of step_ptr [2] (the slot that accept call wrote) and its acceptance mh = alphas[c, t] (alphas
+ *   [C, nmcmc + 1] as qn_hmc_accept fills it), a = min(1, mh) with NaN counted as 0, and advances the dual averaging of
+ *   Hoffman & Gelman 2014 (algorithm 5; gamma = 0.05, t0 = 10, kappa = 0.75), m >= 1 the index of this step in the current run:
+ *     Hbar = (1 - 1/(m+t0)) Hbar + (target_accept - a)/(m+t0);  logeps = mu - sqrt(m)/gamma * Hbar;
+ *     logbar = m^-kappa logeps + (1 - m^-kappa) logbar;         eps[c] = exp(logeps)
+ *   on da [C, 4] = (mu, Hbar, logbar, logeps); a run starts from (log(10 eps0), 0, 0, any).  freeze (the last warm-up step):
+ *   eps[c] = exp(logbar) instead.  collect: Welford update of mean / m2 [C, p] with the state cur [C, p], n >= 1 the number
+ *   of states collected including this one: d = x - mean; mean += d / n; m2 += d * (x - mean).  finish (a window end, n >= 2;
+ *   after the update of the same call): scale = sqrt((n/(n+5)) * m2/(n-1) + 1e-3 * 5/(n+5)), mean = m2 = 0, and dual averaging
+ *   restarts around the new step size: mu = log(10 eps[c]), Hbar = logbar = 0 (the caller's next m is 1).  finish and freeze
+ *   exclude each other.  m, n and the flags are host-known: nothing is read back, no atomics; cur / mean / m2 / scale may be
+ *   NULL when neither collect nor finish is set. */
+int qn_hmc_begin_s(const double* cur, const double* grad_cur, double sigma, const double* eps, const double* scale, int C,
+                   int chain0, int64_t p, uint64_t seed, const int64_t* step_ptr, double* mom, double* q,
+                   double* kin_cur_parts, void* stream);
+int qn_hmc_leap_s(const void* grad_q, int dtype, double sigma, const double* eps, const double* scale, int last, int C,
+                  int64_t p, double* mom, double* q, double* kin_prop_parts, void* stream);
+int qn_hmc_adapt(const double* cur, const double* alphas, int nmcmc, const int64_t* step_ptr, int parity, int C, int64_t p,
+                 int m, double target_accept, int collect, int finish, int freeze, int n, double* da, double* eps,
+                 double* mean, double* m2, double* scale, void* stream);
+
 /* Moments of a predictive ensemble on the device (QUiNNBase.predict_mom_sample, quinn/solvers/quinn.py:75-104):
  * Y [M, K] dtype = M members x K = N * o prediction entries as qn_mlp_sse_fwd writes them ([B, Nb, o] with B = M);
  * mean_out [K], var_out [K] (unbiased, ddof = 1; NULL to skip; needs M >= 2), float64.  The per-output covariance of

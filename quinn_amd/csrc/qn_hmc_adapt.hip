@@ -1,0 +1,241 @@
+// Device HMC / MALA with a per-chain step size and a diagonal mass matrix, and their warm-up adaptation:
+//   qn_hmc_begin_s / qn_hmc_leap_s : the leapfrog kernels of qn_mcmc.hip (k_hmc_begin / k_hmc_leap) with eps a DEVICE array
+//                                    [C] and an optional per-parameter scale [C, p] (square root of the inverse mass)
+//   qn_hmc_adapt                   : one launch per warm-up step after the accept call: dual averaging of the step size
+//                                    (Hoffman & Gelman 2014, algorithm 5) and Welford moments of the state for the scale
+// The leapfrog runs in whitened momenta u = s * r (r the momentum, M^-1 = diag(s^2)): u ~ N(0, I), K = |u|^2 / 2, a kick is
+// u += (f eps_c) s * d logpost, a drift q += eps_c s * u -- the kernels of qn_mcmc.hip with the scalars half_kick / kick / eps
+// replaced by the per-element products (kick_c * s) and (eps_c * s).  Same grid, same element -> thread map, same Philox keys
+// and the same fixed-order partial sums, so with scale = 1 and equal eps_c the results are those kernels' bit for bit, and
+// qn_hmc_accept serves both.  HBM-bound elementwise work; all stores are ordinary vector stores, no atomics, no fences.
+#include "qn_mcmc_shared.h"
+
+namespace {
+
+// mom = z + (hk_c s) g_cur;  q = cur + (eps_c s) mom;  K_cur partial = sum z^2       (hk_c = (eps_c / 2) gs, gs = -0.5 / sigma^2)
+// One Philox block = one PAIR of consecutive elements = one 16-byte access per array (8-byte aligned: rows of odd length).
+__global__ __launch_bounds__(HBLK) void k_hmc_begin_s(const double* __restrict__ cur, const double* __restrict__ gcur,
+                                                      const double* __restrict__ eps, const double* __restrict__ scale,
+                                                      double gs, int chain0, int64_t p, uint64_t seed,
+                                                      const int64_t* __restrict__ step_ptr, double* __restrict__ mom,
+                                                      double* __restrict__ q, double* __restrict__ kin_parts) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const uint64_t step = (uint64_t)*step_ptr;
+    const double eps_c = eps[b];
+    const double half_kick = 0.5 * eps_c * gs;
+    const int64_t base = (int64_t)b * p;
+    const int64_t npair = (p + 1) / 2;
+    const int64_t pchunk = (npair + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = blockIdx.x * pchunk, hi = lo + pchunk < npair ? lo + pchunk : npair;
+    double ss = 0.0;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += HBLK) {
+        Philox ph;
+        ph.gen(seed, 2 * step, ctr_of(chain0 + b, 0, (uint64_t)j));
+        double za, zb;
+        normal2(ph, za, zb);
+        const int64_t e = 2 * j;
+        const bool both = e + 1 < p;
+        const d2u one = {1.0, 1.0};
+        const d2u gv = ld2(gcur + base + e, both), cv = ld2(cur + base + e, both);
+        const d2u sv = scale ? ld2(scale + base + e, both) : one;
+        const double m0 = fma(half_kick * sv.x, gv.x, za);
+        const double q0 = fma(eps_c * sv.x, m0, cv.x);
+        ss = fma(za, za, ss);
+        double m1 = 0.0, q1 = 0.0;
+        if (both) {
+            m1 = fma(half_kick * sv.y, gv.y, zb);
+            q1 = fma(eps_c * sv.y, m1, cv.y);
+            ss = fma(zb, zb, ss);
+        }
+        st2(mom + base + e, m0, m1, both);
+        st2(q + base + e, q0, q1, both);
+    }
+    const double tot = block_sum_256(ss, red);
+    if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
+}
+
+// mom += (kick_c s) g;   last ? K_prop partial = sum mom^2 : q += (eps_c s) mom        (kick_c = f eps_c gs, f = 1 or 1/2)
+// The element -> thread map and the order of the sum of squares are k_hmc_leap's.  HS: a scale array is given (a compile-time
+// choice, so that the unrolled loads carry no per-element branch).
+template <typename TG, bool HS>
+__global__ __launch_bounds__(HBLK) void k_hmc_leap_s(const TG* __restrict__ g, const double* __restrict__ eps,
+                                                     const double* __restrict__ scale, double f, double gs, int last,
+                                                     int64_t p, double* __restrict__ mom, double* __restrict__ q,
+                                                     double* __restrict__ kin_parts) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const double eps_c = eps[b];
+    const double kick = f * eps_c * gs;
+    const int64_t base = (int64_t)b * p;
+    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
+    double ss = 0.0;
+    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
+        double gv[HUB], mv[HUB], qv[HUB], sv[HUB];
+#pragma unroll
+        for (int u = 0; u < HUB; ++u) {
+            const int64_t e = e0 + (int64_t)u * HBLK;
+            const bool in = e < hi;
+            gv[u] = in ? (double)g[base + e] : 0.0;
+            mv[u] = in ? mom[base + e] : 0.0;
+            qv[u] = (in && !last) ? q[base + e] : 0.0;
+            sv[u] = (HS && in) ? scale[base + e] : 1.0;
+        }
+#pragma unroll
+        for (int u = 0; u < HUB; ++u) {
+            const int64_t e = e0 + (int64_t)u * HBLK;
+            if (e >= hi) break;
+            const double m = fma(kick * sv[u], gv[u], mv[u]);
+            mom[base + e] = m;
+            if (last) ss = fma(m, m, ss);
+            else q[base + e] = fma(eps_c * sv[u], m, qv[u]);
+        }
+    }
+    if (last) {
+        const double tot = block_sum_256(ss, red);
+        if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
+    }
+}
+
+// One warm-up step's adaptation.  Scalars (workgroup 0 of the chain, thread 0): the acceptance of the step just decided
+// is alphas[c, t] with t = step_ptr[par] (the slot the accept call wrote); a = min(1, mh), NaN -> 0;
+//   Hbar = (1 - w) Hbar + (target - a) w;  logeps = mu - sg Hbar;  logbar = eta logeps + (1 - eta) logbar
+// with the host-computed w = 1 / (m + t0), sg = sqrt(m) / gamma, eta = m^-kappa; eps_c = exp(logeps), or exp(logbar) when
+// the warm-up ends (freeze); at a window end (finish) dual averaging restarts around the new step: mu = log(10 eps_c),
+// Hbar = logbar = 0.  da [C, 4] = (mu, Hbar, logbar, logeps).
+// Elements (all workgroups of the chain, pairs of elements as 16-byte accesses): collect -- Welford update with the
+// host-known count n; finish -- scale = sqrt(c0 * M2 / (n - 1) + c1), then mean = M2 = 0.
+struct AdaptArgs {
+    int nmcmc, par, collect, finish, freeze;
+    int64_t p;
+    double w, sg, eta, target;
+    double n, nm1, c0, c1;          // n, n - 1, n / (n + 5), 1e-3 * 5 / (n + 5)
+};
+constexpr int WPT = 2;              // pairs per thread and pass
+__global__ __launch_bounds__(HBLK) void k_hmc_adapt(AdaptArgs a, const double* __restrict__ cur,
+                                                    const double* __restrict__ alphas,
+                                                    const int64_t* __restrict__ step_ptr, double* __restrict__ da,
+                                                    double* __restrict__ eps, double* __restrict__ mean,
+                                                    double* __restrict__ m2, double* __restrict__ scale) {
+    const int b = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t t = step_ptr[a.par];
+        const double mh = (t >= 0 && t <= a.nmcmc) ? alphas[(int64_t)b * (a.nmcmc + 1) + t] : 0.0;
+        const double acc = (mh == mh) ? fmin(1.0, mh) : 0.0;                 // NaN (a diverged trajectory) counts as 0
+        double mu = da[4 * b], hbar = da[4 * b + 1], logbar = da[4 * b + 2];
+        hbar = (1.0 - a.w) * hbar + (a.target - acc) * a.w;
+        const double logeps = mu - a.sg * hbar;
+        logbar = a.eta * logeps + (1.0 - a.eta) * logbar;
+        const double e = a.freeze ? exp(logbar) : exp(logeps);
+        if (a.finish) { mu = log(10.0 * e); hbar = 0.0; logbar = 0.0; }
+        da[4 * b] = mu; da[4 * b + 1] = hbar; da[4 * b + 2] = logbar; da[4 * b + 3] = logeps;
+        eps[b] = e;
+    }
+    if (!a.collect && !a.finish) return;
+    const int64_t base = (int64_t)b * a.p;
+    const int64_t npair = (a.p + 1) / 2;
+    const int64_t stride = (int64_t)gridDim.x * (WPT * HBLK);
+    for (int64_t pair0 = (int64_t)blockIdx.x * (WPT * HBLK) + threadIdx.x; pair0 < npair; pair0 += stride) {
+        d2u xv[WPT], mv[WPT], sv[WPT];
+#pragma unroll
+        for (int h = 0; h < WPT; ++h) {
+            const int64_t pair = pair0 + (int64_t)h * HBLK, e = 2 * pair;
+            const bool in = pair < npair, both = e + 1 < a.p;
+            const d2u zero = {0.0, 0.0};
+            xv[h] = (in && a.collect) ? ld2(cur + base + e, both) : zero;
+            mv[h] = (in && a.collect) ? ld2(mean + base + e, both) : zero;
+            sv[h] = in ? ld2(m2 + base + e, both) : zero;
+        }
+#pragma unroll
+        for (int h = 0; h < WPT; ++h) {
+            const int64_t pair = pair0 + (int64_t)h * HBLK, e = 2 * pair;
+            if (pair >= npair) break;
+            const bool both = e + 1 < a.p;
+            d2u mn = mv[h], s2 = sv[h];
+            if (a.collect) {
+                const double d0 = xv[h].x - mn.x, d1 = xv[h].y - mn.y;
+                mn.x += d0 / a.n; mn.y += d1 / a.n;
+                s2.x += d0 * (xv[h].x - mn.x); s2.y += d1 * (xv[h].y - mn.y);
+            }
+            if (a.finish) {
+                st2(scale + base + e, sqrt(a.c0 * (s2.x / a.nm1) + a.c1), sqrt(a.c0 * (s2.y / a.nm1) + a.c1), both);
+                mn.x = mn.y = s2.x = s2.y = 0.0;
+            }
+            st2(mean + base + e, mn.x, mn.y, both);
+            st2(m2 + base + e, s2.x, s2.y, both);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int qn_hmc_begin_s(const double* cur, const double* grad_cur, double sigma, const double* eps,
+                              const double* scale, int C, int chain0, int64_t p, uint64_t seed, const int64_t* step_ptr,
+                              double* mom, double* q, double* kin_cur_parts, void* stream) {
+    if (!cur || !grad_cur || !eps || !step_ptr || !mom || !q || !kin_cur_parts || C <= 0 || C > 65535 || chain0 < 0 ||
+        p <= 0 || !(sigma > 0.0)) {
+        qn_set_error("qn_hmc_begin_s: bad argument");
+        return QN_EINVAL;
+    }
+    const double gs = -0.5 / (sigma * sigma);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_hmc_begin_s, dim3(hmc_parts(p), C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), cur, grad_cur,
+                       eps, scale, gs, chain0, p, seed, step_ptr, mom, q, kin_cur_parts);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}
+
+extern "C" int qn_hmc_leap_s(const void* grad_q, int dtype, double sigma, const double* eps, const double* scale, int last,
+                             int C, int64_t p, double* mom, double* q, double* kin_prop_parts, void* stream) {
+    if (!grad_q || !eps || !mom || !q || (last && !kin_prop_parts) || C <= 0 || C > 65535 || p <= 0 || !(sigma > 0.0) ||
+        (dtype != QN_F64 && dtype != QN_F32)) {
+        qn_set_error("qn_hmc_leap_s: bad argument");
+        return QN_EINVAL;
+    }
+    const double gs = -0.5 / (sigma * sigma);
+    const double f = last ? 0.5 : 1.0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    const dim3 grid(hmc_parts(p), C), blk(HBLK);
+    const int l = last ? 1 : 0;
+    if (dtype == QN_F32 && scale)
+        hipLaunchKernelGGL((k_hmc_leap_s<float, true>), grid, blk, 0, st, (const float*)grad_q, eps, scale, f, gs, l, p, mom, q,
+                           kin_prop_parts);
+    else if (dtype == QN_F32)
+        hipLaunchKernelGGL((k_hmc_leap_s<float, false>), grid, blk, 0, st, (const float*)grad_q, eps, scale, f, gs, l, p, mom, q,
+                           kin_prop_parts);
+    else if (scale)
+        hipLaunchKernelGGL((k_hmc_leap_s<double, true>), grid, blk, 0, st, (const double*)grad_q, eps, scale, f, gs, l, p, mom,
+                           q, kin_prop_parts);
+    else
+        hipLaunchKernelGGL((k_hmc_leap_s<double, false>), grid, blk, 0, st, (const double*)grad_q, eps, scale, f, gs, l, p, mom,
+                           q, kin_prop_parts);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}
+
+extern "C" int qn_hmc_adapt(const double* cur, const double* alphas, int nmcmc, const int64_t* step_ptr, int parity, int C,
+                            int64_t p, int m, double target_accept, int collect, int finish, int freeze, int n, double* da,
+                            double* eps, double* mean, double* m2, double* scale, void* stream) {
+    if (!alphas || !step_ptr || !da || !eps || C <= 0 || C > 65535 || p <= 0 || nmcmc < 1 || m < 1 ||
+        (parity != 0 && parity != 1) || !(target_accept > 0.0 && target_accept < 1.0) ||
+        (collect && (!cur || !mean || !m2 || n < 1)) || (finish && (!mean || !m2 || !scale || n < 2)) ||
+        (finish && freeze)) {
+        qn_set_error("qn_hmc_adapt: bad argument (collect needs cur / mean / m2 and n >= 1, finish needs scale and n >= 2, "
+                     "finish and freeze exclude each other)");
+        return QN_EINVAL;
+    }
+    const double t0 = 10.0, gamma = 0.05, kappa = 0.75;        // Stan's constants
+    AdaptArgs a;
+    a.nmcmc = nmcmc; a.par = parity; a.collect = collect ? 1 : 0; a.finish = finish ? 1 : 0; a.freeze = freeze ? 1 : 0;
+    a.p = p;
+    a.w = 1.0 / (m + t0); a.sg = std::sqrt((double)m) / gamma; a.eta = std::pow((double)m, -kappa); a.target = target_accept;
+    a.n = n; a.nm1 = n - 1.0; a.c0 = n / (n + 5.0); a.c1 = 1e-3 * (5.0 / (n + 5.0));
+    const int gx = (collect || finish) ? hmc_parts(p) : 1;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_hmc_adapt, dim3(gx, C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), a, cur, alphas, step_ptr,
+                       da, eps, mean, m2, scale);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}

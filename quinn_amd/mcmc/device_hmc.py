@@ -16,6 +16,13 @@ of steps (parity 0, 1) are captured once in a HIP graph and replayed.  Random st
 chain id): a chain's path does not depend on how the chains are split over ranks or launches (only the summation order
 of its SSE does, through the row split the gradient kernel picks for the batch size).  Chains agree with the host `HMC`
 in distribution, not bit for bit (Philox instead of numpy's MT19937).
+
+`adapt` > 0 warm-up steps tune a per-chain step size and, with `adapt_mass`, a per-chain diagonal mass matrix on the device
+(`quinn_amd.mcmc.adapt` states the contract): every step then runs qn_hmc_begin_s / qn_hmc_leap_s, which read the step
+sizes [C] and the scales [C, p] from device arrays; a warm-up step is followed by one qn_hmc_adapt launch whose schedule
+(window ends, counts) is static and host-known, so still nothing is read back.  Warm-up rows are stored like any other row
+(discard them with `nburn`); the results gain 'epsilon' [C], 'mass_scale' [C, p] (None without mass windows) and 'nwarm'.
+adapt = 0 (default) runs the fixed-step kernels exactly as before.
 """
 import ctypes
 
@@ -24,13 +31,22 @@ import torch
 
 from .. import _lib
 from ..ops import BatchedMLP
+from .adapt import TARGET_ACCEPT, check_adapt_args, warmup_plan
 
 
 class DeviceHMC:
-    def __init__(self, op: BatchedMLP, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None):
+    _kind = 'hmc'
+
+    def __init__(self, op: BatchedMLP, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
+                 target_accept=None, adapt_mass=True):
         self.op, self.sigma, self.epsilon, self.L = op, float(sigma), float(epsilon), int(L)
         if self.L < 1:
             raise ValueError("HMC needs L >= 1 leapfrog steps")
+        # warm-up: `adapt` steps of dual averaging from `epsilon` towards `target_accept` (default 0.8; MALA 0.574) and, with
+        # adapt_mass, Stan's mass windows; 0: the fixed-step kernels
+        self.target_accept = TARGET_ACCEPT[self._kind] if target_accept is None else float(target_accept)
+        self.adapt = check_adapt_args(adapt, self.target_accept)
+        self.adapt_mass = bool(adapt_mass)
         # groups > 1: the chains run as that many independent groups on their own HIP streams, enqueued step by step from this
         # one host thread; a group's gradient launch splits a chain's rows as the launch of all chains would
         # (qn_mlp_desc_set_plan_batch), so the chains do not depend on the number of groups, bit for bit.  Default 1: unlike the
@@ -73,6 +89,40 @@ class DeviceHMC:
             s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], st), "qn_hmc_accept")
         s['par'] ^= 1
 
+    def _step_s(self, s, nmcmc):
+        """`_step` with the per-chain step sizes s['eps'] and scales s['scale'] (None: 1) read on the device."""
+        Lb, st = self._L, self._stream()
+        C, p = s['cur'].shape
+        step_ptr = s['step'].data_ptr() + 8 * s['par']
+        eps, scale = s['eps'].data_ptr(), (None if s['scale'] is None else s['scale'].data_ptr())
+        _lib.check(Lb.qn_hmc_begin_s(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, eps, scale, C, self.chain0, p,
+                                     self.seed, step_ptr, s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st),
+                   "qn_hmc_begin_s")
+        for j in range(self.L):
+            last = j == self.L - 1
+            qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])
+            self.op.sse_grad(qc, out=(s['sse'], s['gq']))
+            _lib.check(Lb.qn_hmc_leap_s(s['gq'].data_ptr(), self.op.qdt, self.sigma, eps, scale, int(last), C, p,
+                                        s['mom'].data_ptr(), s['q'].data_ptr(), s['kprop'].data_ptr(), st), "qn_hmc_leap_s")
+        g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
+        _lib.check(Lb.qn_hmc_accept(
+            s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
+            self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
+            s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
+            s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
+            s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], st), "qn_hmc_accept")
+        s['par'] ^= 1
+
+    def _adapt_step(self, s, nmcmc, a):
+        """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
+        from the slot of the step counter the accept call wrote, which is s['par'] after `_step_s`."""
+        C, p = s['cur'].shape
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self._L.qn_hmc_adapt(s['cur'].data_ptr(), s['alphas'].data_ptr(), nmcmc, s['step'].data_ptr(), s['par'], C, p,
+                                        a['m'], self.target_accept, int(a['collect']), int(a['finish']), int(a['freeze']),
+                                        a['n'], s['da'].data_ptr(), s['eps'].data_ptr(), ptr(s['wmean']), ptr(s['wm2']),
+                                        ptr(s['scale']), self._stream()), "qn_hmc_adapt")
+
     def _ngroups(self, C):
         if self.groups is None:
             return 1
@@ -93,7 +143,8 @@ class DeviceHMC:
         if self._subs is None or [e.chain0 - self.chain0 for e in self._subs[0]] != bounds[:-1]:
             op = self.op
             engs = [DeviceHMC(BatchedMLP(op.arch, op.X, op.Y, device=op.device, dtype=op.dtype), self.sigma, self.epsilon,
-                              self.L, self.seed, self.chain0 + bounds[g], self.use_graph, groups=1) for g in range(G)]
+                              self.L, self.seed, self.chain0 + bounds[g], self.use_graph, groups=1, adapt=self.adapt,
+                              target_accept=self.target_accept, adapt_mass=self.adapt_mass) for g in range(G)]
             for e in engs:
                 e.op.set_plan_batch(max(C, op.set_plan_batch(-1)))
                 path = op.set_path(_lib.PATH_AUTO)                            # (the kernel family forced on the parent, if any)
@@ -120,10 +171,15 @@ class DeviceHMC:
             main.wait_stream(st)
         out = {k: torch.cat([r[k] for r in res]) for k in ('mapparams', 'maxpost', 'accrate', 'logpost', 'alphas')}
         out['chain'] = chain
+        if self.adapt:
+            out['epsilon'] = torch.cat([r['epsilon'] for r in res])
+            out['mass_scale'] = None if res[0]['mass_scale'] is None else torch.cat([r['mass_scale'] for r in res])
+            out['nwarm'] = self.adapt
         return out
 
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
+        check_adapt_args(self.adapt, self.target_accept, nmcmc)
         dev, f64 = self.dev, torch.float64
         cur = torch.as_tensor(param_ini, dtype=f64, device=dev).clone().reshape(-1, self.op.p)
         C, p = cur.shape
@@ -148,19 +204,37 @@ class DeviceHMC:
             s['chain'][:, 0] = cur
         s['lps'][:, 0] = cur_lp
         i = 0
-        if self.use_graph and nmcmc >= 4:
+        step = self._step
+        if self.adapt:
+            # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
+            step = self._step_s
+            plan = warmup_plan(self.adapt, self.adapt_mass)
+            mass = any(a['finish'] for a in plan)
+            s['eps'] = torch.full((C,), self.epsilon, dtype=f64, device=dev)
+            s['da'] = torch.zeros(C, 4, dtype=f64, device=dev)          # (mu, Hbar, logbar, logeps)
+            s['da'][:, 0] = np.log(10 * self.epsilon)
+            s['da'][:, 3] = np.log(self.epsilon)
+            s['scale'] = torch.ones(C, p, dtype=f64, device=dev) if mass else None
+            s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
+            s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
+            for a in plan:
+                self._step_s(s, nmcmc)
+                self._adapt_step(s, nmcmc, a)
+                i += 1
+                yield
+        if self.use_graph and nmcmc - i >= 4:
             # two steps (parity 0 and 1) captured once; warm the kernels up on a side stream first (torch's capture rule)
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
-                self._step(s, nmcmc)
-                self._step(s, nmcmc)
+                step(s, nmcmc)
+                step(s, nmcmc)
             torch.cuda.current_stream(dev).wait_stream(side)
-            i = 2
+            i += 2
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self._step(s, nmcmc)
-                self._step(s, nmcmc)
+                step(s, nmcmc)
+                step(s, nmcmc)
             i += 2                                         # (capture does not run the kernels: replay once for steps 2, 3)
             graph.replay()
             yield
@@ -171,10 +245,13 @@ class DeviceHMC:
                 if verbose and nmcmc >= 10 and i % max(2, (nmcmc // 10) // 2 * 2) == 0:
                     print('%d / %d completed, acceptance rate %lg' % (i, nmcmc, float(s['nacc'].double().mean()) / i))
         while i < nmcmc:
-            self._step(s, nmcmc)
+            step(s, nmcmc)
             i += 1
             yield
             if verbose and nmcmc >= 10 and (i + 1) % (nmcmc // 10) == 0:
                 print('%d / %d completed, acceptance rate %lg' % (i + 1, nmcmc, float(s['nacc'].double().mean()) / i))
-        return {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][s['par']].clone(),
-                'accrate': s['nacc'].double() / max(nmcmc, 1), 'logpost': s['lps'], 'alphas': s['alphas']}
+        out = {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][s['par']].clone(),
+               'accrate': s['nacc'].double() / max(nmcmc, 1), 'logpost': s['lps'], 'alphas': s['alphas']}
+        if self.adapt:
+            out.update(epsilon=s['eps'], mass_scale=s['scale'], nwarm=self.adapt)
+        return out

@@ -19,7 +19,11 @@ from .device_hmc import DeviceHMC
 
 
 class DeviceMALA(DeviceHMC):
-    """Args as `MALA` (epsilon: step size, default 0.05) plus the engine's seed / chain0 / use_graph / groups."""
+    """Args as `MALA` (epsilon: step size, default 0.05) plus the engine's seed / chain0 / use_graph / groups and the warm-up
+    arguments adapt / target_accept (default 0.574) / adapt_mass of `DeviceHMC`."""
+    _kind = 'mala'
 
-    def __init__(self, op, sigma, epsilon=0.05, seed=0, chain0=0, use_graph=False, groups=None):
-        super().__init__(op, sigma, epsilon=epsilon, L=1, seed=seed, chain0=chain0, use_graph=use_graph, groups=groups)
+    def __init__(self, op, sigma, epsilon=0.05, seed=0, chain0=0, use_graph=False, groups=None, adapt=0, target_accept=None,
+                 adapt_mass=True):
+        super().__init__(op, sigma, epsilon=epsilon, L=1, seed=seed, chain0=chain0, use_graph=use_graph, groups=groups,
+                         adapt=adapt, target_accept=target_accept, adapt_mass=adapt_mass)

@@ -7,19 +7,22 @@ raises UnboundLocalError) `NN_MCMC.fit(sampler='mala')` reaches this class.
 """
 import numpy as np
 
-from .mcmc import MCMCBase
-from .hmc import _kinetic
+from .hmc import AdaptiveLeapfrog, _kinetic
 
 
-class MALA(MCMCBase):
-    """Args: epsilon (float): step size (default 0.05)."""
+class MALA(AdaptiveLeapfrog):
+    """Args: epsilon (float): step size (default 0.05).
+    Build-only: adapt / target_accept (default 0.574) / adapt_mass as `HMC`: MALA is the leapfrog with L = 1."""
 
-    def __init__(self, epsilon=0.05):
+    def __init__(self, epsilon=0.05, adapt=0, target_accept=None, adapt_mass=True):
         super().__init__()
         self.epsilon = epsilon
+        self._init_adapt(adapt, target_accept, adapt_mass, 'mala')
 
     def sampler_batch(self, current, imcmc):
         assert self.logPostGrad is not None or self.logPostGradBatch is not None
+        if self.adapt:
+            return self._whitened_leapfrog(current, 1)
         C, p = current.shape
         eps = self.epsilon
         q = current.copy()

@@ -93,6 +93,7 @@ class MCMCBase(object):
         lps[:, 0] = -cur_U
         nacc = np.zeros(C, dtype=np.int64)
         acc_rate = np.zeros(C)
+        self._run_start(cur, nmcmc)
 
         for i in range(nmcmc):
             prop, k_cur, k_prop = self.sampler_batch(cur, i)
@@ -111,15 +112,29 @@ class MCMCBase(object):
             chain[:, i + 1] = cur
             alphas[:, i + 1] = mh
             lps[:, i + 1] = -cur_U
+            self._step_done(i, cur, mh)
             acc_rate = nacc / float(i + 1)
             if verbose and nmcmc >= 10 and ((i + 2) % (nmcmc / 10) == 0 or i == nmcmc - 2):
                 print('%d / %d completed, acceptance rate %lg' % (i + 2, nmcmc, float(np.mean(acc_rate))))
 
+        extras = self._run_extras()
         if single:
             return {'chain': chain[0], 'mapparams': best[0], 'maxpost': float(best_lp[0]),
-                    'accrate': float(acc_rate[0]), 'logpost': lps[0], 'alphas': alphas[0]}
+                    'accrate': float(acc_rate[0]), 'logpost': lps[0], 'alphas': alphas[0],
+                    **{k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in extras.items()}}
         return {'chain': chain, 'mapparams': best, 'maxpost': best_lp, 'accrate': acc_rate,
-                'logpost': lps, 'alphas': alphas}
+                'logpost': lps, 'alphas': alphas, **extras}
+
+    # -- hooks of samplers that adapt during the run (HMC / MALA warm-up); no-ops here ---------
+    def _run_start(self, cur, nmcmc):
+        pass
+
+    def _step_done(self, i, cur, mh):
+        """After the accept decision of step i: cur (C,p) the new states, mh (C,) the step's MH ratios."""
+
+    def _run_extras(self):
+        """Further entries of the result dict (arrays with a leading chain axis, or scalars)."""
+        return {}
 
     # -- proposals --------------------------------------------------------------------
     def sampler_batch(self, current, imcmc):

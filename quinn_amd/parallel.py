@@ -133,9 +133,12 @@ def all_gather_rows(local, n_total):
 def gather_results(res, n_total, gather="all", gather_chain=None, max_bytes=DEFAULT_MAX_GATHER_BYTES):
     """Gather a sampler's result dict (`chain`, `mapparams`, `maxpost`, `accrate`, `logpost`, `alphas`; device
     tensors or numpy, this rank's shard) -> dict of numpy arrays.  The small entries follow `gather`; `chain`
-    ([C, nmcmc+1, p], the large one: 43.6 GB per rank at cfg2) follows `gather_chain` (None: the same as `gather`)."""
+    ([C, nmcmc+1, p], the large one: 43.6 GB per rank at cfg2) follows `gather_chain` (None: the same as `gather`).
+    Adapted HMC / MALA runs add the per-chain `epsilon` [C] and `mass_scale` [C, p] (gathered like the small entries) and
+    the scalar `nwarm`, which is the same on every rank and passed through."""
     gc = gather if gather_chain is None else gather_chain
-    return {k: (None if v is None else gather_rows(v, n_total, dst=gc if k == "chain" else gather, max_bytes=max_bytes))
+    return {k: (v if v is None or np.isscalar(v) else
+                gather_rows(v, n_total, dst=gc if k == "chain" else gather, max_bytes=max_bytes))
             for k, v in res.items()}
 
 
@@ -159,14 +162,26 @@ def run_chains_sharded(make_sampler, nmcmc, param_ini, seeds, verbose=False, gat
     if hi > lo:
         res = mc.run(nmcmc, ini, rngs=rngs, verbose=verbose)
     else:
-        res = empty_results(nmcmc, ini.shape[1])
-    return gather_results({k: np.asarray(v) for k, v in res.items()}, C, gather, gather_chain)
+        res = empty_results(nmcmc, ini.shape[1], *adapt_keys(getattr(mc, 'adapt', 0), getattr(mc, 'adapt_mass', True)))
+    return gather_results({k: (v if v is None or np.isscalar(v) else np.asarray(v)) for k, v in res.items()}, C, gather,
+                          gather_chain)
 
 
-def empty_results(nmcmc, p):
-    """Result dict of a rank that owns no chain (fewer chains than ranks)."""
-    return {'chain': np.zeros((0, nmcmc + 1, p)), 'mapparams': np.zeros((0, p)), 'maxpost': np.zeros(0),
-            'accrate': np.zeros(0), 'logpost': np.zeros((0, nmcmc + 1)), 'alphas': np.zeros((0, nmcmc + 1))}
+def adapt_keys(adapt, adapt_mass):
+    """(adapt, mass) arguments of `empty_results` for a sampler's warm-up settings."""
+    from .mcmc.adapt import warmup_plan
+    adapt = int(adapt or 0)
+    return adapt, bool(adapt) and any(a['finish'] for a in warmup_plan(adapt, adapt_mass))
+
+
+def empty_results(nmcmc, p, adapt=0, mass=False):
+    """Result dict of a rank that owns no chain (fewer chains than ranks).  adapt > 0: with the keys of an adapted HMC /
+    MALA run (mass: the run has mass windows, so `mass_scale` is an array on the ranks that own chains)."""
+    out = {'chain': np.zeros((0, nmcmc + 1, p)), 'mapparams': np.zeros((0, p)), 'maxpost': np.zeros(0),
+           'accrate': np.zeros(0), 'logpost': np.zeros((0, nmcmc + 1)), 'alphas': np.zeros((0, nmcmc + 1))}
+    if adapt:
+        out.update(epsilon=np.zeros(0), mass_scale=np.zeros((0, p)) if mass else None, nwarm=int(adapt))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ launcher

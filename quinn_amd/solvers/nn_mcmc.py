@@ -22,7 +22,7 @@ from ..mcmc.hmc import HMC
 from ..mcmc.mala import MALA
 from ..mcmc import diagnostics as diag
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
-from ..parallel import dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
+from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
 
 
@@ -129,6 +129,10 @@ class NN_MCMC(QUiNNBase):
         Build-only: nchains (C independent chains in lock-step), seeds (C ints; chain c then
             equals a reference run preceded by np.random.seed(seeds[c])).  With nchains=1 and
             seeds=None the global numpy RNG is used, exactly like the reference.
+            sampler_params of 'hmc' / 'mala' may hold adapt=K (both engines): the first K <= nmcmc steps are a warm-up that
+            tunes a per-chain step size from `epsilon` by dual averaging (target_accept, default 0.8 / 0.574) and, unless
+            adapt_mass=False, a per-chain diagonal mass matrix (`quinn_amd.mcmc.adapt`); `mcmc_results` then also holds
+            'epsilon', 'mass_scale' and 'nwarm', and the warm-up rows stay in the chain (discard them with nburn >= K).
             engine='device' (samplers 'amcmc', 'hmc' and 'mala'): states, proposal factors and history stay on the
             GPU, no host synchronisation per step (`quinn_amd.mcmc.device_amcmc`); same target and
             adaptation schedule, chains equal the host engine in distribution, not bit for bit.  The device AMCMC keeps at most
@@ -198,6 +202,9 @@ class NN_MCMC(QUiNNBase):
             param_ini = np.tile(param_ini, (nchains, 1))
 
         sampler_params = dict(sampler_params)      # None raises, as in the reference
+        nadapt = int(sampler_params.get('adapt', 0) or 0)
+        if nadapt > nmcmc:
+            raise ValueError(f"sampler_params['adapt'] = {nadapt} warm-up steps exceed nmcmc = {nmcmc}")
         if engine == 'device':
             op = self._operator(self.lpinfo)
             ini2 = np.atleast_2d(param_ini)
@@ -220,7 +227,7 @@ class NN_MCMC(QUiNNBase):
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
             else:
-                res = empty_results(nmcmc, ini2.shape[1])
+                res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)))
             if diagnostics:
                 # from the engine's device tensors, before they are downloaded (or not: gather_chain='none')
                 self.diagnostics = self._fit_diagnostics(res['chain'], res['logpost'], diag_nburn, ctot, gather)
@@ -228,7 +235,7 @@ class NN_MCMC(QUiNNBase):
             res = gather_results(res, ctot, gather, gather_chain)
             self.mcmc_results = res
             if np.ndim(param_ini) == 1:
-                self.mcmc_results = {k: v[0] for k, v in self.mcmc_results.items()}
+                self.mcmc_results = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in self.mcmc_results.items()}
             self.samples, self.cmode = self.mcmc_results['chain'], self.mcmc_results['mapparams']
             return
         if sampler == 'amcmc':
