@@ -640,30 +640,45 @@ static int accept_parts(int64_t p) {                   // workgroups per chain: 
     const int64_t n = ((p + 1) / 2 + APT * ABLK - 1) / (APT * ABLK);
     return n > APARTS_MAX ? APARTS_MAX : (n < 1 ? 1 : (int)n);
 }
+// The one launch of k_accept behind qn_mcmc_accept, qn_mcmc_accept_propose and qn_hmc_accept.  `bad`: the refusals of the
+// entry point `who` beyond the common ones; a arrives with what the entry points differ in (kcap, pstride, nparts, hscale and
+// the HMC fields) and is completed here; the history arrays are null for HMC.
+static int accept_launch(const char* who, bool bad, AcceptArgs a, const NextArgs& nx, const double* prop, const double* sse_prop,
+                         double sigma, int n_rows, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, double* cur,
+                         double* cur_lp, double* best, double* best_lp, double* chain, double* lps, double* alphas,
+                         int64_t* nacc, const double* x0, void* hist, int32_t* mult, int32_t* kcur, double* sumx,
+                         int64_t* step_ptr, int parity, void* stream) {
+    if (bad || !prop || !sse_prop || !cur || !cur_lp || !best || !best_lp || !lps || !alphas || !nacc || !step_ptr || C <= 0 ||
+        C > 65535 || chain0 < 0 || p <= 0 || (parity != 0 && parity != 1)) {
+        qn_set_error("%s: bad argument", who);
+        return QN_EINVAL;
+    }
+    a.half_inv_sig2 = 0.5 / (sigma * sigma);
+    a.lp_const = 0.5 * n_rows * std::log(2.0 * M_PI) + n_rows * std::log(sigma);
+    a.chain0 = chain0; a.nmcmc = nmcmc; a.p = p; a.seed = seed; a.par = parity; a.C = C;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_accept, dim3(accept_parts(p), C), dim3(ABLK), 0, static_cast<hipStream_t>(stream), a, prop, sse_prop, cur, cur_lp,
+                       best, best_lp, chain, lps, alphas, nacc, x0, static_cast<half_t*>(hist), mult, kcur, sumx, step_ptr, nx);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}
+static AcceptArgs accept_args_mcmc(int kcap, int64_t pstride, int nparts, const double* hscale) {      // plain Metropolis
+    AcceptArgs a;
+    a.kcap = kcap; a.pstride = pstride; a.nparts = nparts; a.hscale = hscale;
+    a.nkin = 0; a.kin_cur = a.kin_prop = a.gprop = nullptr; a.gcur = nullptr;
+    return a;
+}
+static const NextArgs NEXT_NONE = {0, 0, 0.0, 0.0, nullptr, nullptr, nullptr};
+
 extern "C" int qn_mcmc_accept(const double* prop, const double* sse_prop, double sigma, int n_rows, int C, int chain0,
                               int64_t p, int nmcmc, uint64_t seed, double* cur, double* cur_lp, double* best, double* best_lp,
                               double* chain, double* lps, double* alphas, int64_t* nacc, const double* x0,
                               void* hist, const double* hscale, int32_t* mult, int32_t* kcur, double* sumx, int kcap,
                               int64_t pstride, int64_t* step_ptr, int parity, int nparts, void* stream) {
-    if (!prop || !sse_prop || !cur || !cur_lp || !best || !best_lp || !lps || !alphas || !nacc || !step_ptr ||
-        C <= 0 || C > 65535 || chain0 < 0 || p <= 0 || sigma <= 0.0 || (parity != 0 && parity != 1) || nparts < 1 ||
-        (hist && (!x0 || !mult || !kcur || !sumx || kcap <= 0 || pstride < p))) {
-        qn_set_error("qn_mcmc_accept: bad argument");
-        return QN_EINVAL;
-    }
-    AcceptArgs a;
-    a.half_inv_sig2 = 0.5 / (sigma * sigma);
-    a.lp_const = 0.5 * n_rows * std::log(2.0 * M_PI) + n_rows * std::log(sigma);
-    a.chain0 = chain0; a.nmcmc = nmcmc; a.kcap = kcap; a.p = p; a.pstride = pstride; a.seed = seed;
-    a.par = parity; a.C = C; a.nparts = nparts; a.hscale = hscale;
-    a.nkin = 0; a.kin_cur = a.kin_prop = a.gprop = nullptr; a.gcur = nullptr;
-    (void)hipGetLastError();
-    NextArgs nx;
-    nx.mode = 0; nx.t = 0; nx.c1 = 0.0; nx.s_iso = 0.0; nx.sd = nullptr; nx.delta = nullptr; nx.out = nullptr;
-    hipLaunchKernelGGL(k_accept, dim3(accept_parts(p), C), dim3(ABLK), 0, static_cast<hipStream_t>(stream), a, prop, sse_prop, cur, cur_lp,
-                       best, best_lp, chain, lps, alphas, nacc, x0, static_cast<half_t*>(hist), mult, kcur, sumx, step_ptr, nx);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
+    const bool bad = sigma <= 0.0 || nparts < 1 || (hist && (!x0 || !mult || !kcur || !sumx || kcap <= 0 || pstride < p));
+    return accept_launch("qn_mcmc_accept", bad, accept_args_mcmc(kcap, pstride, nparts, hscale), NEXT_NONE, prop, sse_prop, sigma,
+                         n_rows, C, chain0, p, nmcmc, seed, cur, cur_lp, best, best_lp, chain, lps, alphas, nacc, x0, hist, mult,
+                         kcur, sumx, step_ptr, parity, stream);
 }
 
 extern "C" int qn_mcmc_accept_propose(const double* prop, const double* sse_prop, double sigma, int n_rows, int C,
@@ -673,26 +688,13 @@ extern "C" int qn_mcmc_accept_propose(const double* prop, const double* sse_prop
                                       int32_t* kcur, double* sumx, int kcap, int64_t pstride, int64_t* step_ptr, int next_mode,
                                       const double* sd, double c1, const double* delta, int t_next, double s_iso,
                                       double* prop_next, int parity, int nparts, void* stream) {
-    if (!prop || !sse_prop || !cur || !cur_lp || !best || !best_lp || !lps || !alphas || !nacc || !step_ptr ||
-        C <= 0 || C > 65535 || chain0 < 0 || p <= 0 || sigma <= 0.0 || (parity != 0 && parity != 1) || nparts < 1 || (hist && (!x0 || !mult || !kcur || !sumx || kcap <= 0 || pstride < p)) ||
-        next_mode < 0 || next_mode > 2 || (next_mode && !prop_next) || (next_mode == 1 && !sd) ||
-        (next_mode == 2 && (!delta || t_next < 0 || t_next >= TB))) {
-        qn_set_error("qn_mcmc_accept_propose: bad argument");
-        return QN_EINVAL;
-    }
-    AcceptArgs a;
-    a.half_inv_sig2 = 0.5 / (sigma * sigma);
-    a.lp_const = 0.5 * n_rows * std::log(2.0 * M_PI) + n_rows * std::log(sigma);
-    a.chain0 = chain0; a.nmcmc = nmcmc; a.kcap = kcap; a.p = p; a.pstride = pstride; a.seed = seed;
-    a.par = parity; a.C = C; a.nparts = nparts; a.hscale = hscale;
-    a.nkin = 0; a.kin_cur = a.kin_prop = a.gprop = nullptr; a.gcur = nullptr;
-    NextArgs nx;
-    nx.mode = next_mode; nx.t = t_next; nx.c1 = c1; nx.s_iso = s_iso; nx.sd = sd; nx.delta = delta; nx.out = prop_next;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_accept, dim3(accept_parts(p), C), dim3(ABLK), 0, static_cast<hipStream_t>(stream), a, prop, sse_prop, cur, cur_lp,
-                       best, best_lp, chain, lps, alphas, nacc, x0, static_cast<half_t*>(hist), mult, kcur, sumx, step_ptr, nx);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
+    const bool bad = sigma <= 0.0 || nparts < 1 || (hist && (!x0 || !mult || !kcur || !sumx || kcap <= 0 || pstride < p)) ||
+                     next_mode < 0 || next_mode > 2 || (next_mode && !prop_next) || (next_mode == 1 && !sd) ||
+                     (next_mode == 2 && (!delta || t_next < 0 || t_next >= TB));
+    const NextArgs nx = {next_mode, t_next, c1, s_iso, sd, delta, prop_next};
+    return accept_launch("qn_mcmc_accept_propose", bad, accept_args_mcmc(kcap, pstride, nparts, hscale), nx, prop, sse_prop, sigma,
+                         n_rows, C, chain0, p, nmcmc, seed, cur, cur_lp, best, best_lp, chain, lps, alphas, nacc, x0, hist, mult,
+                         kcur, sumx, step_ptr, parity, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- HMC entry points
@@ -740,24 +742,10 @@ extern "C" int qn_hmc_accept(const double* q, const double* grad_q, const double
                              uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best, double* best_lp,
                              double* chain, double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr, int parity,
                              void* stream) {
-    if (!q || !grad_q || !sse_q || !kin_cur_parts || !kin_prop_parts || !cur || !grad_cur || !cur_lp || !best || !best_lp ||
-        !lps || !alphas || !nacc || !step_ptr || C <= 0 || C > 65535 || chain0 < 0 || p <= 0 || !(sigma > 0.0) ||
-        (parity != 0 && parity != 1)) {
-        qn_set_error("qn_hmc_accept: bad argument");
-        return QN_EINVAL;
-    }
+    const bool bad = !grad_q || !kin_cur_parts || !kin_prop_parts || !grad_cur || !(sigma > 0.0);
     AcceptArgs a;
-    a.half_inv_sig2 = 0.5 / (sigma * sigma);
-    a.lp_const = 0.5 * n_rows * std::log(2.0 * M_PI) + n_rows * std::log(sigma);
-    a.chain0 = chain0; a.nmcmc = nmcmc; a.kcap = 0; a.p = p; a.pstride = p; a.seed = seed;
-    a.par = parity; a.C = C; a.nparts = 1; a.hscale = nullptr;
+    a.kcap = 0; a.pstride = p; a.nparts = 1; a.hscale = nullptr;
     a.nkin = hmc_parts(p); a.kin_cur = kin_cur_parts; a.kin_prop = kin_prop_parts; a.gprop = grad_q; a.gcur = grad_cur;
-    NextArgs nx;
-    nx.mode = 0; nx.t = 0; nx.c1 = 0.0; nx.s_iso = 0.0; nx.sd = nullptr; nx.delta = nullptr; nx.out = nullptr;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_accept, dim3(accept_parts(p), C), dim3(ABLK), 0, static_cast<hipStream_t>(stream), a, q, sse_q, cur,
-                       cur_lp, best, best_lp, chain, lps, alphas, nacc, (const double*)nullptr, (half_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, step_ptr, nx);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
+    return accept_launch("qn_hmc_accept", bad, a, NEXT_NONE, q, sse_q, sigma, n_rows, C, chain0, p, nmcmc, seed, cur, cur_lp, best,
+                         best_lp, chain, lps, alphas, nacc, nullptr, nullptr, nullptr, nullptr, nullptr, step_ptr, parity, stream);
 }

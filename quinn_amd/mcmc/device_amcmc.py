@@ -34,28 +34,45 @@ Same target distribution and the same adaptation schedule as the reference; the 
 differ (Philox instead of numpy MT19937, sample-space draw instead of an SVD factor), so chains agree
 with the host sampler in distribution, not bit for bit.  Use `AMCMC` for bit-exact parity.
 """
-import ctypes
 import os
+import sys
+import time
 
 import numpy as np
 import torch
 
 from .. import _lib
-from ..ops import BatchedMLP
+from .device_engine import DeviceEngine
 
 
-class DeviceAMCMC:
-    def __init__(self, op: BatchedMLP, sigma, gamma=0.1, t0=100, tadapt=1000, cov_ini=None, seed=0,
+def _tic(dev):
+    """QN_AMCMC_TIMING set (diagnostic: synchronising timings of a window's phases): the time after a synchronisation; else None."""
+    if not os.environ.get("QN_AMCMC_TIMING"):
+        return None
+    torch.cuda.synchronize(dev)
+    return time.perf_counter()
+
+
+def _toc(dev, t0, what, *args):
+    """Print `what % (*args, ms since t0 = _tic(dev))`; nothing when t0 is None."""
+    if t0 is not None:
+        torch.cuda.synchronize(dev)
+        print("[timing] step " + what % (*args, 1e3 * (time.perf_counter() - t0)), flush=True, file=sys.stderr)
+
+
+class DeviceAMCMC(DeviceEngine):
+    def __init__(self, op, sigma, gamma=0.1, t0=100, tadapt=1000, cov_ini=None, seed=0,
                  use_graph=False, max_history_bytes=64 << 30, chain0=0, fuse_propose=True, groups=None, max_rows=4096,
                  overlap_hist=True, hist_scale0=256.0, pause_gc=True):
         if op.dtype != "float64":
             raise NotImplementedError("the device AMCMC engine runs the float64 operator")
-        self.op, self.sigma = op, float(sigma)
+        # groups > 1: a group's accept / propose kernel (a chain of memory round trips that leaves the GPU idle: 8.7 of a step's
+        # 84 us at cfg2) overlaps the other group's forward kernel.  None: 2 groups from 32 chains on (measured at cfg2: 11.9 ->
+        # 12.4 k steps/s before the first adaptation; 4 groups are bound by the enqueuing thread) when the fused kernels run the
+        # network, else 1
+        super().__init__(op, sigma, seed, chain0, use_graph, groups)
         self.gamma, self.t0, self.tadapt = gamma, int(t0), int(tadapt)
         self.cov_ini = cov_ini
-        self.dev = op.device
-        self.seed = int(seed) & (2 ** 63 - 1)
-        self.use_graph = use_graph
         self.max_history_bytes = int(max_history_bytes)
         # bound on the stored rows per chain (p float32 each).  When a chain's history could overflow before the next
         # adaptation it is COMPRESSED in sample space (`_compress_history`: same multiplicity total and mean, scatter
@@ -66,14 +83,6 @@ class DeviceAMCMC:
         # box: 2-3 % slower while the accept kernel ran one workgroup per chain, 1 % faster now that it spreads a
         # chain over several)
         self.fuse_propose = bool(fuse_propose)
-        self.chain0 = int(chain0)      # global id of this engine's first chain (random streams are keyed by it)
-        # groups > 1: the chains are split into that many independent groups, each on its own HIP stream, enqueued
-        # block by block from this one host thread: a group's accept / propose kernel (a chain of memory round trips that
-        # leaves the GPU idle: 8.7 of a step's 84 us at cfg2) overlaps the other group's forward kernel.  The groups' launches
-        # split a chain's rows as the launch of all chains would (qn_mlp_desc_set_plan_batch): the chains do not depend on
-        # the number of groups, bit for bit.  None: 2 groups from 32 chains on (measured at cfg2: 11.9 -> 12.4 k steps/s
-        # before the first adaptation; 4 groups are bound by the enqueuing thread) when the fused kernels run the network, else 1
-        self.groups = None if groups is None else max(1, int(groups))
         # the increments of the NEXT block of TB steps are formed on a second stream while the current block's steps run
         # (they depend on the frozen snapshot and the step numbers only): the history product streams the chains'
         # histories from HBM, the log-posterior kernel is bound by vector issue, and the accept kernels leave most of the
@@ -87,18 +96,8 @@ class DeviceAMCMC:
         self.pause_gc = bool(pause_gc)
         self.overlap_hist = bool(overlap_hist) and not os.environ.get("QUINN_AMD_NO_HIST_OVERLAP")
         self._side = None
-        self._subs = None
-        self._L = _lib.lib()
 
     # -- kernel wrappers (enqueue on the current stream) ---------------------------------------------
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
-    @staticmethod
-    def _step_ptr(s):
-        """Pointer to the CURRENT slot of the double-buffered device step counter (include/quinn_amd.h)."""
-        return s['step'].data_ptr() + 8 * s['par']
-
     def _propose(self, cur, sd, c1, s, out):
         C, p = out.shape
         _lib.check(self._L.qn_mcmc_propose(cur.data_ptr() if cur is not None else None,
@@ -124,28 +123,22 @@ class DeviceAMCMC:
                    "qn_mcmc_apply_delta")
 
     def _accept(self, s, prop, sse, nmcmc, nxt=None):
-        """sse: [C] or [C, parts] (partial sums, added left to right by the kernel)."""
+        """sse: [C] or [C, parts] (partial sums, added left to right by the kernel).  nxt: the accept kernel also writes the
+        next step's proposal (mode, sd, c1, delta, t, s_iso)."""
         C, p = prop.shape
         nparts = sse.shape[1] if sse.dim() == 2 else 1
-        if nxt is not None:
-            mode, sd, c1, delta, t, s_iso = nxt
-            _lib.check(self._L.qn_mcmc_accept_propose(
-                prop.data_ptr(), sse.data_ptr(), self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed,
-                s['cur'].data_ptr(), s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
+        args = (prop.data_ptr(), sse.data_ptr(), self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(),
+                s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
                 s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
                 s['nacc'].data_ptr(), s['x0'].data_ptr(), s['hist'].data_ptr(), s['hscale'].data_ptr(), s['mult'].data_ptr(),
-                s['kcur'].data_ptr(), s['sumx'].data_ptr(), s['hist'].shape[1], s['hist'].shape[2], s['step'].data_ptr(),
-                mode, sd.data_ptr() if sd is not None else None, c1, delta.data_ptr() if delta is not None else None,
+                s['kcur'].data_ptr(), s['sumx'].data_ptr(), s['hist'].shape[1], s['hist'].shape[2], s['step'].data_ptr())
+        if nxt is None:
+            _lib.check(self._L.qn_mcmc_accept(*args, s['par'], nparts, self._stream()), "qn_mcmc_accept")
+        else:
+            mode, sd, c1, delta, t, s_iso = nxt
+            _lib.check(self._L.qn_mcmc_accept_propose(
+                *args, mode, sd.data_ptr() if sd is not None else None, c1, delta.data_ptr() if delta is not None else None,
                 int(t), s_iso, prop.data_ptr(), s['par'], nparts, self._stream()), "qn_mcmc_accept_propose")
-            s['par'] ^= 1
-            return
-        _lib.check(self._L.qn_mcmc_accept(
-            prop.data_ptr(), sse.data_ptr(), self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(),
-            s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
-            s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
-            s['nacc'].data_ptr(), s['x0'].data_ptr(), s['hist'].data_ptr(), s['hscale'].data_ptr(), s['mult'].data_ptr(),
-            s['kcur'].data_ptr(), s['sumx'].data_ptr(), s['hist'].shape[1], s['hist'].shape[2],
-            s['step'].data_ptr(), s['par'], nparts, self._stream()), "qn_mcmc_accept")
         s['par'] ^= 1              # the kernel read slot `par` of the per-chain scalars / step counter and wrote the other
 
     def _ngroups(self, C):
@@ -162,65 +155,24 @@ class DeviceAMCMC:
         if was:
             gc.disable()
         try:
-            return self._run(nmcmc, param_ini, store_chain, verbose)
+            return super().run(nmcmc, param_ini, store_chain, verbose)
         finally:
             if was:
                 gc.enable()
 
-    def _run(self, nmcmc, param_ini, store_chain=True, verbose=False):
-        ini = torch.as_tensor(np.asarray(param_ini), dtype=torch.float64, device=self.dev).reshape(-1, self.op.p)
-        C, p = ini.shape
-        G = self._ngroups(C)
-        if G <= 1:
-            gen = self._run_gen(nmcmc, ini, store_chain, verbose)
-            while True:
-                try:
-                    next(gen)
-                except StopIteration as e:
-                    return e.value
-        # ---- several groups of chains side by side
-        bounds = [C * g // G for g in range(G + 1)]
+    def _check_groups(self, nmcmc, C, p):
         pstride = (p + 3) // 4 * 4
         if C * self._kcap(nmcmc) * pstride * 2 > self.max_history_bytes:
             raise MemoryError(f"state history {C} x {self._kcap(nmcmc)} x {pstride} float16 exceeds max_history_bytes="
                               f"{self.max_history_bytes}: lower max_rows or raise the limit")
-        if self._subs is None or [e.chain0 - self.chain0 for e in self._subs[0]] != bounds[:-1]:
-            op = self.op
-            engs = [DeviceAMCMC(BatchedMLP(op.arch, op.X, op.Y, device=op.device, dtype=op.dtype), self.sigma, self.gamma,
-                                self.t0, self.tadapt, self.cov_ini, self.seed, self.use_graph, self.max_history_bytes,
-                                self.chain0 + bounds[g], self.fuse_propose, max_rows=self.max_rows,
-                                overlap_hist=self.overlap_hist, hist_scale0=self.hist_scale0, pause_gc=False)
-                    for g in range(G)]
-            for e in engs:
-                # a group's launches split every chain's rows as the launch of all C chains does: each chain's SSE is summed in
-                # the same order, so the chains are those of groups = 1 bit for bit (include/quinn_amd.h)
-                e.op.set_plan_batch(max(C, op.set_plan_batch(-1)))
-                path = op.set_path(_lib.PATH_AUTO)                            # (the kernel family forced on the parent, if any)
-                op.set_path(path)
-                e.op.set_path(path)
-            self._subs = (engs, [torch.cuda.Stream(device=self.dev) for _ in range(G)])
-        engs, streams = self._subs
-        chain = torch.empty(C, nmcmc + 1, p, dtype=torch.float64, device=self.dev) if store_chain else None
-        gens = [engs[g]._run_gen(nmcmc, ini[bounds[g]:bounds[g + 1]], store_chain, verbose and g == 0,
-                                 chain_out=None if chain is None else chain[bounds[g]:bounds[g + 1]]) for g in range(G)]
-        main = torch.cuda.current_stream(self.dev)
-        for st in streams:
-            st.wait_stream(main)
-        res, live = [None] * G, list(range(G))
-        while live:
-            for g in list(live):
-                with torch.cuda.stream(streams[g]):
-                    try:
-                        next(gens[g])
-                    except StopIteration as e:
-                        res[g] = e.value
-                        live.remove(g)
-        for st in streams:
-            main.wait_stream(st)
-        out = {k: torch.cat([r[k] for r in res]) for k in ('mapparams', 'maxpost', 'accrate', 'logpost', 'alphas')}
-        out['chain'] = chain
+
+    def _clone(self, op, chain0):
+        return DeviceAMCMC(op, self.sigma, self.gamma, self.t0, self.tadapt, self.cov_ini, self.seed, self.use_graph,
+                           self.max_history_bytes, chain0, self.fuse_propose, max_rows=self.max_rows,
+                           overlap_hist=self.overlap_hist, hist_scale0=self.hist_scale0, pause_gc=False)
+
+    def _merge_groups(self, out, res, engs):
         self.last_state, self.last_states = None, [e.last_state for e in engs]      # (diagnostics: per group)
-        return out
 
     @staticmethod
     def _sum_of_samples(s):
@@ -431,9 +383,6 @@ class DeviceAMCMC:
         dev, f64 = self.dev, torch.float64
         cur = torch.as_tensor(param_ini, dtype=f64, device=dev).clone().reshape(-1, self.op.p)
         C, p = cur.shape
-        n = self.op.N
-        const = (n / 2) * np.log(2 * np.pi) + n * np.log(self.sigma)
-        cur_lp = -(0.5 * self.op.sse(cur) / self.sigma ** 2 + const)
         # history of distinct states: one row per accepted move at most -> nmcmc + 1 rows always suffice; capped at
         # max_rows (thinned when it could fill up before the next adaptation)
         kcap, pstride = self._kcap(nmcmc), (p + 3) // 4 * 4
@@ -445,25 +394,14 @@ class DeviceAMCMC:
         if C * kcap * pstride * 2 + extra > self.max_history_bytes:
             raise MemoryError(f"state history {C} x {kcap} x {pstride} float16 (+ {extra >> 20} MiB of compression work space) exceeds max_history_bytes="
                               f"{self.max_history_bytes}: lower max_rows or raise the limit")
-        # per-chain scalars the accept kernel maintains are double-buffered by step parity ([2, C]; slot `par` is current)
-        s = {'cur': cur, 'cur_lp': torch.stack([cur_lp, cur_lp]), 'best': cur.clone(),
-             'best_lp': torch.stack([cur_lp, cur_lp]), 'x0': cur.clone(), 'par': 0,
-             'chain': (chain_out if chain_out is not None else torch.empty(C, nmcmc + 1, p, dtype=f64, device=dev))
-                      if store_chain else None,
-             'lps': torch.empty(C, nmcmc + 1, dtype=f64, device=dev),
-             'alphas': torch.zeros(C, nmcmc + 1, dtype=f64, device=dev),
-             'nacc': torch.zeros(C, dtype=torch.int64, device=dev),
-             'hist': torch.empty(C, kcap, pstride, dtype=torch.float16, device=dev),
-             'hscale': torch.full((C,), self.hist_scale0, dtype=f64, device=dev),
-             'mult': torch.zeros(C, kcap, dtype=torch.int32, device=dev),
-             'kcur': torch.zeros(2, C, dtype=torch.int32, device=dev),
-             'sumx': torch.zeros(C, p, dtype=f64, device=dev),
-             'step': torch.zeros(2, dtype=torch.int64, device=dev)}
+        s = self._new_state(cur, self.op.sse(cur), nmcmc, store_chain, chain_out)
+        s.update({'x0': cur.clone(), 'hist': torch.empty(C, kcap, pstride, dtype=torch.float16, device=dev),
+                  'hscale': torch.full((C,), self.hist_scale0, dtype=f64, device=dev),
+                  'mult': torch.zeros(C, kcap, dtype=torch.int32, device=dev),
+                  'kcur': torch.zeros(2, C, dtype=torch.int32, device=dev),
+                  'sumx': torch.zeros(C, p, dtype=f64, device=dev)})
         s['hist'][:, 0] = 0.0                                               # row 0 = x_0 - x_0
         s['mult'][:, 0] = 1
-        if store_chain:
-            s['chain'][:, 0] = cur
-        s['lps'][:, 0] = cur_lp
         std0 = torch.sqrt(0.09 * s['x0'].abs())
         prop = torch.empty(C, p, dtype=f64, device=dev)
         state = {'snap': None, 'L': None, 'have_prop': False, 'dbuf': 0, 'ahead': None}
@@ -544,16 +482,10 @@ class DeviceAMCMC:
         while i < nmcmc:
             if kcap < nmcmc + 1 and i > 0:
                 # room for every step up to the next check (each may append a row); compress the chains that lack it
-                if os.environ.get("QN_AMCMC_TIMING"):
-                    import time as _time
-                    torch.cuda.synchronize(dev); _tc = _time.perf_counter()
+                t0 = _tic(dev)
                 ncomp = self._compress_history(s, min(nmcmc, (i // self.tadapt + 1) * self.tadapt) - i + 1, p, step=i)
-                if os.environ.get("QN_AMCMC_TIMING"):
-                    torch.cuda.synchronize(dev); print("[timing] step %d: compression of %d chains %.1f ms" % (i, ncomp, 1e3 * (_time.perf_counter() - _tc)), flush=True, file=__import__("sys").stderr)
-            _tm = os.environ.get("QN_AMCMC_TIMING")                          # (diagnostic: synchronising timings of the window's phases)
-            if _tm:
-                import time as _time
-                torch.cuda.synchronize(dev); _t0 = _time.perf_counter()
+                _toc(dev, t0, "%d: compression of %d chains %.1f ms", i, ncomp)
+            t0 = _tic(dev)
             if i > self.t0 and i % self.tadapt == 0:
                 # adaptation (admcmc.py:66-67) = snapshot of the history x_0..x_i: n = i + 1 samples
                 scale = self.gamma * 2.4 ** 2 / p
@@ -565,8 +497,7 @@ class DeviceAMCMC:
                 graphs = {k: g for k, g in graphs.items() if k[0] != 'adapted'}   # new snapshot tensors: recapture
                 if coef is None:
                     coef, delta = self.prepare(nmcmc, C)
-            if _tm:
-                torch.cuda.synchronize(dev); print("[timing] step %d: snapshot / allocation %.1f ms" % (i, 1e3 * (_time.perf_counter() - _t0)), flush=True, file=__import__("sys").stderr)
+            _toc(dev, t0, "%d: snapshot / allocation %.1f ms", i)
             nrun = min(nmcmc, (i // self.tadapt + 1) * self.tadapt) - i     # up to the next adaptation
             adapted = state['snap'] is not None
             nfull, rest = divmod(nrun, G)
@@ -587,11 +518,9 @@ class DeviceAMCMC:
                 rest = nrun
             if adapted:
                 while rest > 0:
-                    if _tm and rest == nrun:
-                        torch.cuda.synchronize(dev); _t1 = _time.perf_counter()
+                    t0 = _tic(dev) if rest == nrun else None
                     block_adapted(min(rest, TB), None if self.use_graph else i + nrun - rest, rest > TB)
-                    if _tm and rest == nrun:
-                        torch.cuda.synchronize(dev); print("[timing] step %d: first adapted block of %d steps %.1f ms" % (i, min(rest, TB), 1e3 * (_time.perf_counter() - _t1)), flush=True, file=__import__("sys").stderr)
+                    _toc(dev, t0, "%d: first adapted block of %d steps %.1f ms", i, min(rest, TB))
                     rest -= min(rest, TB)
                     yield
             else:
@@ -606,5 +535,4 @@ class DeviceAMCMC:
                 print('%d / %d completed, acceptance rate %lg' % (i, nmcmc, float(s['nacc'].double().mean()) / i))
         s['sumx'] = self._sum_of_samples(s)     # (the run is over: the current state's stay enters the sum)
         self.last_state = s            # (tests / diagnostics: history rows, multiplicities, sum of all samples)
-        return {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][s['par']].clone(),
-                'accrate': s['nacc'].double() / max(nmcmc, 1), 'logpost': s['lps'], 'alphas': s['alphas']}
+        return self._results(s, nmcmc)

@@ -24,88 +24,49 @@ sizes [C] and the scales [C, p] from device arrays; a warm-up step is followed b
 (discard them with `nburn`); the results gain 'epsilon' [C], 'mass_scale' [C, p] (None without mass windows) and 'nwarm'.
 adapt = 0 (default) runs the fixed-step kernels exactly as before.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
-from ..ops import BatchedMLP
 from .adapt import TARGET_ACCEPT, check_adapt_args, warmup_plan
+from .device_engine import DeviceEngine
 
 
-class DeviceHMC:
+class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
-    def __init__(self, op: BatchedMLP, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
+    def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
                  target_accept=None, adapt_mass=True):
-        self.op, self.sigma, self.epsilon, self.L = op, float(sigma), float(epsilon), int(L)
+        # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
+        # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
+        # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
+        self.epsilon, self.L = float(epsilon), int(L)
         if self.L < 1:
             raise ValueError("HMC needs L >= 1 leapfrog steps")
+        super().__init__(op, sigma, seed, chain0, use_graph, groups)
         # warm-up: `adapt` steps of dual averaging from `epsilon` towards `target_accept` (default 0.8; MALA 0.574) and, with
         # adapt_mass, Stan's mass windows; 0: the fixed-step kernels
         self.target_accept = TARGET_ACCEPT[self._kind] if target_accept is None else float(target_accept)
         self.adapt = check_adapt_args(adapt, self.target_accept)
         self.adapt_mass = bool(adapt_mass)
-        # groups > 1: the chains run as that many independent groups on their own HIP streams, enqueued step by step from this
-        # one host thread; a group's gradient launch splits a chain's rows as the launch of all chains would
-        # (qn_mlp_desc_set_plan_batch), so the chains do not depend on the number of groups, bit for bit.  Default 1: unlike the
-        # AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient kernel puts ONE workgroup on a
-        # CU, so a group's launch cannot spread into the CUs the other group's small kernels leave idle -- measured at cfg2:
-        # 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
-        self.groups = None if groups is None else max(1, int(groups))
-        self._subs = None
-        self.dev = op.device
-        self.seed = int(seed) & (2 ** 63 - 1)
-        self.chain0 = int(chain0)          # global id of this engine's first chain (random streams are keyed by it)
-        self.use_graph = bool(use_graph)
-        self._L = _lib.lib()
-        n = op.N
-        self._const = (n / 2) * np.log(2 * np.pi) + n * np.log(self.sigma)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _step(self, s, nmcmc):
-        """Enqueue one HMC step on the current stream (reads slot s['par'] of the scalars, writes the other)."""
-        Lb, st = self._L, self._stream()
+        """Enqueue one HMC step on the current stream (reads slot s['par'] of the scalars, writes the other).  s['kern']: the
+        begin / leap entry points of this run and their step-size arguments -- (epsilon), or with warm-up the device arrays
+        (eps [C], scale [C, p] or None: 1)."""
+        st = self._stream()
         C, p = s['cur'].shape
-        step_ptr = s['step'].data_ptr() + 8 * s['par']
-        _lib.check(Lb.qn_hmc_begin(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, self.epsilon, C, self.chain0, p,
-                                   self.seed, step_ptr, s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st),
-                   "qn_hmc_begin")
+        begin, begin_name, leap, leap_name, eps = s['kern']
+        _lib.check(begin(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, *eps, C, self.chain0, p, self.seed,
+                         self._step_ptr(s), s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st), begin_name)
         for j in range(self.L):
             last = j == self.L - 1
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
-            _lib.check(Lb.qn_hmc_leap(s['gq'].data_ptr(), self.op.qdt, self.sigma, self.epsilon, int(last), C, p,
-                                      s['mom'].data_ptr(), s['q'].data_ptr(), s['kprop'].data_ptr(), st), "qn_hmc_leap")
+            _lib.check(leap(s['gq'].data_ptr(), self.op.qdt, self.sigma, *eps, int(last), C, p, s['mom'].data_ptr(),
+                            s['q'].data_ptr(), s['kprop'].data_ptr(), st), leap_name)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
-        _lib.check(Lb.qn_hmc_accept(
-            s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
-            self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
-            s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
-            s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
-            s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], st), "qn_hmc_accept")
-        s['par'] ^= 1
-
-    def _step_s(self, s, nmcmc):
-        """`_step` with the per-chain step sizes s['eps'] and scales s['scale'] (None: 1) read on the device."""
-        Lb, st = self._L, self._stream()
-        C, p = s['cur'].shape
-        step_ptr = s['step'].data_ptr() + 8 * s['par']
-        eps, scale = s['eps'].data_ptr(), (None if s['scale'] is None else s['scale'].data_ptr())
-        _lib.check(Lb.qn_hmc_begin_s(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, eps, scale, C, self.chain0, p,
-                                     self.seed, step_ptr, s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st),
-                   "qn_hmc_begin_s")
-        for j in range(self.L):
-            last = j == self.L - 1
-            qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])
-            self.op.sse_grad(qc, out=(s['sse'], s['gq']))
-            _lib.check(Lb.qn_hmc_leap_s(s['gq'].data_ptr(), self.op.qdt, self.sigma, eps, scale, int(last), C, p,
-                                        s['mom'].data_ptr(), s['q'].data_ptr(), s['kprop'].data_ptr(), st), "qn_hmc_leap_s")
-        g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
-        _lib.check(Lb.qn_hmc_accept(
+        _lib.check(self._L.qn_hmc_accept(
             s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
             self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
             s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
@@ -115,7 +76,7 @@ class DeviceHMC:
 
     def _adapt_step(self, s, nmcmc, a):
         """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
-        from the slot of the step counter the accept call wrote, which is s['par'] after `_step_s`."""
+        from the slot of the step counter the accept call wrote, which is s['par'] after `_step`."""
         C, p = s['cur'].shape
         ptr = lambda t: None if t is None else t.data_ptr()
         _lib.check(self._L.qn_hmc_adapt(s['cur'].data_ptr(), s['alphas'].data_ptr(), nmcmc, s['step'].data_ptr(), s['par'], C, p,
@@ -128,54 +89,15 @@ class DeviceHMC:
             return 1
         return min(self.groups, C)
 
-    def run(self, nmcmc, param_ini, store_chain=True, verbose=False):
-        ini = torch.as_tensor(np.asarray(param_ini), dtype=torch.float64, device=self.dev).reshape(-1, self.op.p)
-        C, p = ini.shape
-        G = self._ngroups(C)
-        if G <= 1:
-            gen = self._run_gen(nmcmc, ini, store_chain, verbose)
-            while True:
-                try:
-                    next(gen)
-                except StopIteration as e:
-                    return e.value
-        bounds = [C * g // G for g in range(G + 1)]
-        if self._subs is None or [e.chain0 - self.chain0 for e in self._subs[0]] != bounds[:-1]:
-            op = self.op
-            engs = [DeviceHMC(BatchedMLP(op.arch, op.X, op.Y, device=op.device, dtype=op.dtype), self.sigma, self.epsilon,
-                              self.L, self.seed, self.chain0 + bounds[g], self.use_graph, groups=1, adapt=self.adapt,
-                              target_accept=self.target_accept, adapt_mass=self.adapt_mass) for g in range(G)]
-            for e in engs:
-                e.op.set_plan_batch(max(C, op.set_plan_batch(-1)))
-                path = op.set_path(_lib.PATH_AUTO)                            # (the kernel family forced on the parent, if any)
-                op.set_path(path)
-                e.op.set_path(path)
-            self._subs = (engs, [torch.cuda.Stream(device=self.dev) for _ in range(G)])
-        engs, streams = self._subs
-        chain = torch.empty(C, nmcmc + 1, p, dtype=torch.float64, device=self.dev) if store_chain else None
-        gens = [engs[g]._run_gen(nmcmc, ini[bounds[g]:bounds[g + 1]], store_chain, verbose and g == 0,
-                                 chain_out=None if chain is None else chain[bounds[g]:bounds[g + 1]]) for g in range(G)]
-        main = torch.cuda.current_stream(self.dev)
-        for st in streams:
-            st.wait_stream(main)
-        res, live = [None] * G, list(range(G))
-        while live:
-            for g in list(live):
-                with torch.cuda.stream(streams[g]):
-                    try:
-                        next(gens[g])
-                    except StopIteration as e:
-                        res[g] = e.value
-                        live.remove(g)
-        for st in streams:
-            main.wait_stream(st)
-        out = {k: torch.cat([r[k] for r in res]) for k in ('mapparams', 'maxpost', 'accrate', 'logpost', 'alphas')}
-        out['chain'] = chain
+    def _clone(self, op, chain0):
+        return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
+                         target_accept=self.target_accept, adapt_mass=self.adapt_mass)
+
+    def _merge_groups(self, out, res, engs):
         if self.adapt:
             out['epsilon'] = torch.cat([r['epsilon'] for r in res])
             out['mass_scale'] = None if res[0]['mass_scale'] is None else torch.cat([r['mass_scale'] for r in res])
             out['nwarm'] = self.adapt
-        return out
 
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
@@ -186,28 +108,18 @@ class DeviceHMC:
         nk = int(self._L.qn_hmc_parts(p))
         f32op = self.op.tdt != f64
         sse0, g0 = self.op.sse_grad(cur if not f32op else cur.to(self.op.tdt))
-        cur_lp = -(0.5 * sse0 / self.sigma ** 2 + self._const)
-        s = {'cur': cur, 'gcur': g0.double() if f32op else g0.clone(), 'cur_lp': torch.stack([cur_lp, cur_lp]),
-             'best': cur.clone(), 'best_lp': torch.stack([cur_lp, cur_lp]), 'par': 0,
-             'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),
-             'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
-             'qc': torch.empty(C, p, dtype=self.op.tdt, device=dev) if f32op else None,
-             'g64': torch.empty(C, p, dtype=f64, device=dev) if f32op else None,
-             'kcur': torch.empty(C, nk, dtype=f64, device=dev), 'kprop': torch.empty(C, nk, dtype=f64, device=dev),
-             'chain': (chain_out if chain_out is not None else torch.empty(C, nmcmc + 1, p, dtype=f64, device=dev))
-                      if store_chain else None,
-             'lps': torch.empty(C, nmcmc + 1, dtype=f64, device=dev),
-             'alphas': torch.zeros(C, nmcmc + 1, dtype=f64, device=dev),
-             'nacc': torch.zeros(C, dtype=torch.int64, device=dev),
-             'step': torch.zeros(2, dtype=torch.int64, device=dev)}
-        if store_chain:
-            s['chain'][:, 0] = cur
-        s['lps'][:, 0] = cur_lp
+        s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
+        s.update({'gcur': g0.double() if f32op else g0.clone(),
+                  'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),
+                  'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
+                  'qc': torch.empty(C, p, dtype=self.op.tdt, device=dev) if f32op else None,
+                  'g64': torch.empty(C, p, dtype=f64, device=dev) if f32op else None,
+                  'kcur': torch.empty(C, nk, dtype=f64, device=dev), 'kprop': torch.empty(C, nk, dtype=f64, device=dev),
+                  'kern': (self._L.qn_hmc_begin, "qn_hmc_begin", self._L.qn_hmc_leap, "qn_hmc_leap", (self.epsilon,))})
         i = 0
         step = self._step
         if self.adapt:
             # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
-            step = self._step_s
             plan = warmup_plan(self.adapt, self.adapt_mass)
             mass = any(a['finish'] for a in plan)
             s['eps'] = torch.full((C,), self.epsilon, dtype=f64, device=dev)
@@ -217,8 +129,10 @@ class DeviceHMC:
             s['scale'] = torch.ones(C, p, dtype=f64, device=dev) if mass else None
             s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
+            s['kern'] = (self._L.qn_hmc_begin_s, "qn_hmc_begin_s", self._L.qn_hmc_leap_s, "qn_hmc_leap_s",
+                         (s['eps'].data_ptr(), None if s['scale'] is None else s['scale'].data_ptr()))
             for a in plan:
-                self._step_s(s, nmcmc)
+                step(s, nmcmc)
                 self._adapt_step(s, nmcmc, a)
                 i += 1
                 yield
@@ -250,8 +164,7 @@ class DeviceHMC:
             yield
             if verbose and nmcmc >= 10 and (i + 1) % (nmcmc // 10) == 0:
                 print('%d / %d completed, acceptance rate %lg' % (i + 1, nmcmc, float(s['nacc'].double().mean()) / i))
-        out = {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][s['par']].clone(),
-               'accrate': s['nacc'].double() / max(nmcmc, 1), 'logpost': s['lps'], 'alphas': s['alphas']}
+        out = self._results(s, nmcmc)
         if self.adapt:
             out.update(epsilon=s['eps'], mass_scale=s['scale'], nwarm=self.adapt)
         return out

@@ -20,10 +20,15 @@ from scipy.optimize import minimize
 from ..mcmc.admcmc import AMCMC
 from ..mcmc.hmc import HMC
 from ..mcmc.mala import MALA
+from ..mcmc.device_amcmc import DeviceAMCMC
+from ..mcmc.device_hmc import DeviceHMC
+from ..mcmc.device_mala import DeviceMALA
 from ..mcmc import diagnostics as diag
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
+
+DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA}      # fit(engine='device'): sampler -> class
 
 
 class NN_MCMC(QUiNNBase):
@@ -212,18 +217,10 @@ class NN_MCMC(QUiNNBase):
             rank, world = dist_info()
             lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
             seed0 = seeds[0] if seeds else 0
-            if sampler == 'amcmc':
-                from ..mcmc.device_amcmc import DeviceAMCMC
-                # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
-                eng = DeviceAMCMC(op, datanoise, seed=seed0, chain0=lo, **sampler_params)
-            elif sampler == 'hmc':
-                from ..mcmc.device_hmc import DeviceHMC
-                eng = DeviceHMC(op, datanoise, seed=seed0, chain0=lo, **sampler_params)
-            elif sampler == 'mala':
-                from ..mcmc.device_mala import DeviceMALA
-                eng = DeviceMALA(op, datanoise, seed=seed0, chain0=lo, **sampler_params)
-            else:
+            if sampler not in DEVICE_ENGINES:
                 raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc' and 'mala'")
+            # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
+            eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, **sampler_params)
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
             else:
