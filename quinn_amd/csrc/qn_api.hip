@@ -2,9 +2,12 @@
 // families, and the small elementwise kernels of the VI / ensemble trainers.
 #include "qn_common.h"
 #include "qn_fused_args.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include <cmath>
 #include <cstring>
+#include <mutex>
+#include <unordered_set>
 
 static thread_local char g_err[512] = "";
 
@@ -16,6 +19,25 @@ void qn_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* qn_last_error(void) { return g_err; }
+
+int qn_arm_lds(const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::unordered_set<uint64_t> armed;              // (kernel, device)
+    if (bytes > 160 * 1024) {
+        qn_set_error("int8-slice kernel needs %zu bytes of LDS (limit 160 KB)", bytes);
+        return QN_EUNSUPPORTED;
+    }
+    if (bytes <= 64 * 1024) return QN_OK;
+    int dev = 0;
+    QN_HIP_CHECK(hipGetDevice(&dev));
+    const uint64_t key = (uint64_t)(uintptr_t)kernel * 64u + (uint64_t)(dev & 63);
+    std::lock_guard<std::mutex> lock(mu);
+    if (armed.count(key)) return QN_OK;
+    QN_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    armed.insert(key);
+    return QN_OK;
+}
+
 extern "C" const char* qn_version(void) { return "quinn_amd 0.1 gfx950"; }
 extern "C" int qn_mlp_desc_set_path(qn_desc* d, int path) {
     if (!d) return QN_EINVAL;
@@ -194,13 +216,21 @@ static size_t padded_fixup_doubles(const qn_desc* d) {
     }
     return sum + 2 * hmax;
 }
-static size_t padded_head_bytes(const qn_desc* d, int B, int want_grad, size_t el) {
-    return (want_grad ? 2 : 1) * qn_align((size_t)B * d->padded->p * el) + qn_align((size_t)(B + 1) * 64 * sizeof(int)) +
-           qn_align((size_t)B * padded_fixup_doubles(d) * el);
+constexpr int PAD_SLOTS = 64;           // blocks per chain of k_pad_weights at most (one flag slot each)
+struct PaddedLayout { size_t Wp, Gp = QN_WS_NONE, flags, fix_scratch, total; };       // (`total`: where the twin's own workspace begins)
+static PaddedLayout padded_layout(const qn_desc* d, int B, int want_grad, size_t el) {
+    qn_ws_carver c;
+    PaddedLayout w;
+    w.Wp = c.take((size_t)B * d->padded->p * el);
+    if (want_grad) w.Gp = c.take((size_t)B * d->padded->p * el);
+    w.flags = c.take<int>((size_t)(B + 1) * PAD_SLOTS);
+    w.fix_scratch = c.take((size_t)B * padded_fixup_doubles(d) * el);
+    w.total = c.total;
+    return w;
 }
 static size_t fused_ws(const qn_desc* d, int B, int Nb, int want_grad, int dtype) {
     size_t tot = qn_fused_workspace(fused_desc(d), B, Nb, want_grad, dtype);
-    if (d->padded) tot += padded_head_bytes(d, B, want_grad, sizeof(double));
+    if (d->padded) tot += padded_layout(d, B, want_grad, sizeof(double)).total;
     return tot;
 }
 // layer-wise kernels on the padded twin (hidden widths >= 48 that are no multiples of 64; for widths <= 64 this is
@@ -215,7 +245,7 @@ static bool use_padded_generic(const qn_desc* d) {
 }
 static size_t padded_generic_ws(const qn_desc* d, int B, int Nb, int want_grad, int dtype) {
     const size_t el = dtype == QN_F32 ? sizeof(float) : sizeof(double);
-    return qn_generic_workspace(d->padded, B, Nb, want_grad, dtype) + padded_head_bytes(d, B, want_grad, el);
+    return qn_generic_workspace(d->padded, B, Nb, want_grad, dtype) + padded_layout(d, B, want_grad, el).total;
 }
 
 // ---- zero-padding of hidden layers (weights in, gradients out); one thread per element, layer found by offset
@@ -230,7 +260,6 @@ struct PadMap {
 // (blockIdx.y == 0) every input against 2^ebound, chosen so that below it no intermediate value can overflow; flagged chains
 // (flags[b]; flags[B] = an input: every chain) are recomputed from the ORIGINAL weights by k_padded_fixup after the twin's
 // kernels.  Found by tests/fuzz_all.py (x = -inf on a 33-wide network: the reference saturates, the twin returned NaN).
-constexpr int PAD_SLOTS = 64;           // blocks per chain of k_pad_weights at most (one flag slot each)
 template <typename T> __device__ __forceinline__ bool pad_bounded(T v, T bound) { return (v < T(0) ? -v : v) < bound; }   // (NaN: false)
 template <typename T> __global__ void k_pad_weights(PadMap m, const T* __restrict__ W, T* __restrict__ Wp, const T* __restrict__ X,
                                                     int64_t nx, const T* __restrict__ Y, int64_t ny, T bound, int* __restrict__ flags) {
@@ -372,16 +401,16 @@ int run_padded_t(const qn_desc* d, bool generic, int dtype, const T* W, const vo
                  const int32_t* row_idx, int B, int N, int Nb, double* sse, void* pred, T* gradW, void* ws,
                  size_t ws_bytes, hipStream_t st) {
     const qn_desc* q = d->padded;
-    const size_t wbytes = qn_align((size_t)B * q->p * sizeof(T));
-    const size_t head = padded_head_bytes(d, B, gradW != nullptr, sizeof(T));
+    const PaddedLayout lay = padded_layout(d, B, gradW != nullptr, sizeof(T));
+    const size_t head = lay.total;
     if (head > ws_bytes) {
         qn_set_error("workspace too small: need more than %zu bytes, got %zu", head, ws_bytes);
         return QN_EWORKSPACE;
     }
-    T* Wp = static_cast<T*>(ws);
-    T* Gp = gradW ? reinterpret_cast<T*>(static_cast<char*>(ws) + wbytes) : nullptr;
-    int* flags = reinterpret_cast<int*>(static_cast<char*>(ws) + (gradW ? 2 : 1) * wbytes);
-    T* fix_scratch = reinterpret_cast<T*>(reinterpret_cast<char*>(flags) + qn_align((size_t)(B + 1) * 64 * sizeof(int)));
+    T* Wp = qn_ws_at<T>(ws, lay.Wp);
+    T* Gp = qn_ws_at<T>(ws, lay.Gp);
+    int* flags = qn_ws_at<int>(ws, lay.flags);
+    T* fix_scratch = qn_ws_at<T>(ws, lay.fix_scratch);
     const PadMap m = pad_map(d);
     // 2^e below which no product chain of the network can overflow (tanh: only x . W0; otherwise one factor per layer and up
     // to 2^11 terms per sum)
@@ -394,9 +423,9 @@ int run_padded_t(const qn_desc* d, bool generic, int dtype, const T* W, const vo
     hipLaunchKernelGGL(k_pad_weights<T>, dim3(nslots, B), dim3(256), 0, st, m, W, Wp, static_cast<const T*>(X),
                        (int64_t)N * d->dims[0], static_cast<const T*>(Y), (int64_t)N * d->dims[L], (T)std::ldexp(1.0, eb), flags);
     const int rc = generic ? qn_generic_run(q, dtype, Wp, X, Y, row_idx, B, N, Nb, sse, pred, Gp,
-                                            static_cast<char*>(ws) + head, ws_bytes - head, st)
+                                            qn_ws_at<char>(ws, head), ws_bytes - head, st)
                            : qn_fused_run(q, dtype, Wp, X, Y, row_idx, B, N, Nb, sse, pred, Gp,
-                                          static_cast<char*>(ws) + head, ws_bytes - head, st);
+                                          qn_ws_at<char>(ws, head), ws_bytes - head, st);
     if (rc) return rc;
     if (gradW) {
         gx = (int)((d->p + 255) / 256);

@@ -50,6 +50,13 @@ void qn_set_error(const char* fmt, ...);
 
 static inline size_t qn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// Call before launching `kernel` with `bytes` of dynamic LDS: raises the kernel's dynamic-LDS limit to the hardware's 160 KB,
+// once per (kernel, device) -- the attribute is per device, and a kernel's bytes can grow from call to call (deeper network,
+// same template instance).  Nothing to do up to the default limit of 64 KB; more than 160 KB is QN_EUNSUPPORTED.  After the
+// first call for a (kernel, device) its only HIP call is hipGetDevice, so a warmed-up launch path can be captured into a HIP
+// graph.  Defined once (qn_api.hip): the library holds one armed set.
+int qn_arm_lds(const void* kernel, size_t bytes);
+
 // ---- generic (any-shape) path: qn_generic.hip
 size_t qn_generic_workspace(const qn_desc* d, int B, int Nb, int want_grad, int dtype);
 int qn_generic_run(const qn_desc* d, int dtype, const void* W, const void* X, const void* Y,

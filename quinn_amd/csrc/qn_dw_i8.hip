@@ -28,7 +28,6 @@
 #include "qn_fused_args.h"
 #include "qn_math.h"
 #include "qn_i8_slice.h"
-#include <mutex>
 
 namespace {
 
@@ -809,7 +808,6 @@ int qn_i8_dw(int h_in, int h_out, int has_bias, const double* dz, const double* 
     // group scales (k_i8_dw_g) for row counts in whole chunks; the per-chunk kernel (partial chunks, odd row counts) otherwise
     size_t lds = 2 * (size_t)DW_BUF + 16;
     void (*kern)(DwArgs, const double*, const double*, double*, const double*) = k_i8_dw<QN_I8_LMIN>;
-    int which = 0;
 #if QN_DW_GROUP >= 2
     // (whole 64-row chunks; the caller adds the last Nb % 64 rows with qn_i8_dw_tail behind its split-K reduction)
 #ifdef QN_DW_RAGGED_OLD
@@ -819,22 +817,11 @@ int qn_i8_dw(int h_in, int h_out, int has_bias, const double* dz, const double* 
     if (Nb >= 64 && kchunk % 64 == 0) {
 #endif
         lds = (size_t)DWG_LDS;
-        if (rowsc) { kern = k_i8_dw_g<QN_I8_LMIN, QN_DW_GROUP, true>; which = 2; }
-        else { kern = k_i8_dw_g<QN_I8_LMIN, QN_DW_GROUP, false>; which = 1; }
+        if (rowsc) kern = k_i8_dw_g<QN_I8_LMIN, QN_DW_GROUP, true>;
+        else kern = k_i8_dw_g<QN_I8_LMIN, QN_DW_GROUP, false>;
     }
 #endif
-    {   // raise the dynamic-LDS limit once per device (not per launch: the launch path stays capturable into a HIP graph)
-        static std::mutex mu;
-        static unsigned long long armed[3] = {0, 0, 0};                  // per kernel: bit = device ordinal
-        int dev = 0;
-        QN_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(mu);
-        if (dev < 0 || dev >= 64) return QN_EUNSUPPORTED;
-        if (!(armed[which] >> dev & 1ull)) {
-            QN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            armed[which] |= 1ull << dev;
-        }
-    }
+    if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(DWT), lds, st, g, dz, a_prev, dst, rowsc);
     QN_HIP_CHECK(hipGetLastError());
     return QN_OK;

@@ -23,11 +23,10 @@
 // data row).  SSE partials are reduced in a fixed order (bitwise reproducible).
 #include "qn_common.h"
 #include "qn_fused_args.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include <cstdlib>
 #include <type_traits>
-#include <mutex>
-#include <unordered_set>
 
 // Compiled as two objects: part 0 (this file) holds the kernels' instances with up to 4 inputs (forward, tanh: up to 16) and all
 // the host code; part 1 (qn_fused_d8.hip: `#define QN_FUSED_PART 1` + `#include` of this file) the instances for networks with
@@ -1245,17 +1244,26 @@ void plan(const qn_desc* d, int B, int Nb, int want_grad, FusedArgs* a) {
 #define QN_BWD_TARGET 256
 #endif
     const int target = want_grad || stream ? QN_BWD_TARGET : QN_FWD_TARGET;
-    const int max_split = (Nb + rows_it - 1) / rows_it;
-    const int Bp = d->plan_batch > B ? d->plan_batch : B;
-    int nsplit = (target + Bp - 1) / Bp;
-    if (nsplit > max_split) nsplit = max_split;
-    if (nsplit < 1) nsplit = 1;
-    int rps = (Nb + nsplit - 1) / nsplit;
-    rps = (rps + rows_it - 1) / rows_it * rows_it;
-    nsplit = (Nb + rps - 1) / rps;
-    a->nsplit = nsplit;
-    a->rows_per_split = rps;
-    a->iters = rps / rows_it;
+    const qn_row_split s = qn_plan_row_split(d->plan_batch > B ? d->plan_batch : B, Nb, rows_it, target);
+    a->nsplit = s.nsplit;
+    a->rows_per_split = s.rows_per_split;
+    a->iters = s.iters;
+}
+
+// workspace of a launch: SSE partials [B][nsplit] | arrival counters [B] | gradient calls: slabs [B][nsplit][p] | flags
+// [B][nsplit] of the int8 gradient kernel.  (Diagnostic builds write their stamps behind `total`: the size query's spare 1024 bytes.)
+struct FusedLayout { size_t partial, arrive, slab = QN_WS_NONE, flags = QN_WS_NONE, total; };
+FusedLayout fused_layout(const qn_desc* d, int B, int nsplit, int want_grad) {
+    qn_ws_carver c;
+    FusedLayout w;
+    w.partial = c.take<double>((size_t)B * nsplit);
+    w.arrive = c.take<unsigned long long>((size_t)B);
+    if (want_grad) {
+        w.slab = c.take<double>((size_t)B * nsplit * d->p);
+        w.flags = c.take<int>((size_t)B * nsplit);
+    }
+    w.total = c.total;
+    return w;
 }
 
 constexpr int DBWD = 16;                                   // inputs of the gradient kernel: DP = 4 (part 0), 8 or 16 (part 1)
@@ -1314,21 +1322,6 @@ bwd_fn pick_bwd(int H, int nhid, int act = QN_ACT_TANH, int dp = DMAX, int om = 
     return nullptr;
 }
 
-// raise the dynamic-LDS limit of a kernel once per process (not per launch: keeps the launch
-// function free of non-stream API calls, so it can be captured into a HIP graph)
-int arm_lds(const void* fn) {
-    static std::mutex mu;
-    static std::unordered_set<uint64_t> armed;              // (kernel, device): the attribute is per device
-    int dev = 0;
-    QN_HIP_CHECK(hipGetDevice(&dev));
-    const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)(dev & 63);
-    std::lock_guard<std::mutex> lock(mu);
-    if (armed.count(key)) return QN_OK;
-    QN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    armed.insert(key);
-    return QN_OK;
-}
-
 }  // namespace
 
 bool qn_fused_uses_i8(const qn_desc* d, int want_grad) { return want_grad ? uses_i8_bwd(d) : uses_i8(d, 0); }
@@ -1355,9 +1348,7 @@ bool qn_fused_supported(const qn_desc* d, int B, int Nb, int want_grad, int dtyp
 size_t qn_fused_workspace(const qn_desc* d, int B, int Nb, int want_grad, int dtype) {
     FusedArgs a;
     plan(d, B, Nb, want_grad, &a);
-    size_t tot = qn_align((size_t)B * a.nsplit * sizeof(double)) + qn_align((size_t)B * sizeof(unsigned long long));    // partials | arrivals
-    if (want_grad) tot += qn_align((size_t)B * a.nsplit * d->p * sizeof(double)) + qn_align((size_t)B * a.nsplit * sizeof(int));
-    return tot + 1024;              // (+ a scratch area diagnostic builds write their stamps to)
+    return fused_layout(d, B, a.nsplit, want_grad).total + 1024;    // (+ a scratch area diagnostic builds write their stamps to)
 }
 
 int qn_fused_parts(const qn_desc* d, int B, int Nb) {
@@ -1379,16 +1370,15 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
     a.p = d->p; a.B = B; a.N = N; a.Nb = Nb; a.d = d->dims[0]; a.o = d->dims[d->nlayers]; a.nhid = nhid;
     a.act = d->act; a.has_bias = d->has_bias;
     plan(d, B, Nb, want_grad, &a);
-    const size_t npart = qn_align((size_t)B * a.nsplit * sizeof(double)) + qn_align((size_t)B * sizeof(unsigned long long));
-    const size_t nslab = want_grad ? qn_align((size_t)B * a.nsplit * d->p * sizeof(double)) : 0;
-    const size_t need = npart + nslab + (want_grad ? qn_align((size_t)B * a.nsplit * sizeof(int)) : 0);
-    if (need > ws_bytes) {
-        qn_set_error("workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    const FusedLayout lay = fused_layout(d, B, a.nsplit, want_grad);
+    if (lay.total > ws_bytes) {
+        qn_set_error("workspace too small: need %zu bytes, got %zu", lay.total, ws_bytes);
         return QN_EWORKSPACE;
     }
-    double* partial = (parts_out && !want_grad) ? sse : static_cast<double*>(ws);
-    double* slab = reinterpret_cast<double*>(static_cast<char*>(ws) + npart);
-    a.dbg_off = (int64_t)(need / sizeof(double));          // the 256 spare bytes behind the slabs
+    double* partial = (parts_out && !want_grad) ? sse : qn_ws_at(ws, lay.partial);
+    double* slab = qn_ws_at(ws, lay.slab);
+    unsigned long long* arrive = qn_ws_at<unsigned long long>(ws, lay.arrive);
+    a.dbg_off = (int64_t)(lay.total / sizeof(double));     // the spare bytes behind the slabs
     size_t lds_bytes = lds_need(H, a.d, a.o, nhid, want_grad);
     dim3 grid(qn_fused_grid(a.nsplit, B));
     bool summed = false;
@@ -1406,10 +1396,9 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
             qn_set_error("qn_fused_run: no forward kernel instance for H=%d act=%d", H, a.act);
             return QN_EUNSUPPORTED;
         }
-        if (int rc = arm_lds(reinterpret_cast<const void*>(kern))) return rc;
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return rc;
         // the chain's SSE is summed by the last of its workgroups to finish (qn_sse_finish), unless the caller wants the parts
-        unsigned long long* arrive = partial == sse ? nullptr :
-            reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + qn_align((size_t)B * a.nsplit * sizeof(double)));
+        if (partial == sse) arrive = nullptr;
 #ifdef QN_NO_ARRIVE
         arrive = nullptr;                                   // A/B builds: the separate k_sum_partials launch
 #endif
@@ -1422,15 +1411,16 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
             qn_set_error("qn_fused_run: no backward kernel instance for H=%d nhid=%d", H, nhid);
             return QN_EUNSUPPORTED;
         }
-        if (int rc = arm_lds(reinterpret_cast<const void*>(kern))) return rc;
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return rc;
         const int* flagged = nullptr;
         if (uses_i8_bwd(d)) {
             // sliced int8 products (qn_fused_bwd_i8.hip); (chain, split)s outside its contract are flagged and their chains
             // recomputed by the float64 kernel right behind it (which returns at once for every other chain)
-            int* flags = reinterpret_cast<int*>(static_cast<char*>(ws) + npart + nslab);
+            int* flags = qn_ws_at<int>(ws, lay.flags);
             qn_bwd_i8_fn k8 = qn_fused_bwd_i8_kernel(nhid, a.d, a.act);
-            if (int rc = arm_lds(reinterpret_cast<const void*>(k8))) return rc;
-            hipLaunchKernelGGL(k8, grid, dim3(WG), qn_fused_bwd_i8_lds_bytes(nhid, a.d), st, a, (const double*)W, (const double*)X,
+            const size_t lds8 = qn_fused_bwd_i8_lds_bytes(nhid, a.d);
+            if (int rc = qn_arm_lds(reinterpret_cast<const void*>(k8), lds8)) return rc;
+            hipLaunchKernelGGL(k8, grid, dim3(WG), lds8, st, a, (const double*)W, (const double*)X,
                                (const double*)Y, row_idx, (double*)pred, partial, slab, flags);
             flagged = flags;
         }
@@ -1441,8 +1431,6 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
 #else
         const bool merged = flagged != nullptr;
 #endif
-        unsigned long long* arrive =
-            reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + qn_align((size_t)B * a.nsplit * sizeof(double)));
         hipLaunchKernelGGL(kern, grid, dim3(WG), lds_bytes, st, a, (const double*)W, (const double*)X,
                            (const double*)Y, row_idx, (double*)pred, partial, slab, flagged, merged ? (double*)gradW : (double*)nullptr,
                            sse, arrive);

@@ -10,7 +10,20 @@ struct FusedArgs {
     int64_t dbg_off;     // diagnostic builds: offset (doubles, from the partials) of a 12-word scratch
 };
 
-// Grid of the fused kernels: 1-D and XCD-aware.  Consecutive workgroup ids are dealt round-robin to the 8 XCDs (each
+// Row split of the fused (qn_fused.hip) and the wide int8 (qn_wide_i8.hip) kernels: a chain's Nb rows go to `nsplit` workgroups
+// of `iters` iterations of `rows_it` rows each, so that a launch planned for Bp chains has about `target` workgroups
+struct qn_row_split { int nsplit, rows_per_split, iters; };
+inline qn_row_split qn_plan_row_split(int Bp, int Nb, int rows_it, int target) {
+    const int max_split = (Nb + rows_it - 1) / rows_it;
+    int nsplit = (target + Bp - 1) / Bp;
+    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit < 1) nsplit = 1;
+    int rps = (Nb + nsplit - 1) / nsplit;
+    rps = (rps + rows_it - 1) / rows_it * rows_it;
+    return {(Nb + rps - 1) / rps, rps, rps / rows_it};
+}
+
+// Grid of the fused kernels: 1-D and XCD-aware. Consecutive workgroup ids are dealt round-robin to the 8 XCDs (each
 // with its own L2), so workgroup id -> (chain, row split) is chosen such that all splits of a chain share id % 8: the
 // chain's weights come from HBM once and from that XCD's L2 for the other splits (grid (nsplit, B) put the 8 splits of a
 // cfg2 chain on 8 different XCDs: 8 x the weight traffic, taken as one burst at kernel start).

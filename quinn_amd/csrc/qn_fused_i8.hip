@@ -32,11 +32,10 @@
 // layer-wise kernels.
 #include "qn_common.h"
 #include "qn_fused_args.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include "qn_i8_slice.h"
-#include <mutex>
 #include <type_traits>
-#include <unordered_set>
 #include <utility>
 
 #ifndef QN_I8_G
@@ -935,20 +934,19 @@ bool i8net_of(const qn_desc* d, I8Net* net) {
     return true;
 }
 constexpr size_t i8gemm_lds(int kc) { return (size_t)kc * NS * 64 * 64 + sizeof(double) * (((TANH_TAB + 1) & ~1) + 128); }
-// raise the dynamic-LDS limit of a kernel once per process (not per launch: the launch path stays free of non-stream
-// API calls, so it can be captured into a HIP graph)
-int i8_arm(const void* fn, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_set<uint64_t> armed;              // (kernel, device): the attribute is per device
-    if (bytes <= 64 * 1024) return QN_OK;
-    int dev = 0;
-    QN_HIP_CHECK(hipGetDevice(&dev));
-    const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)(dev & 63);
-    std::lock_guard<std::mutex> lock(mu);
-    if (armed.count(key)) return QN_OK;
-    QN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    armed.insert(key);
-    return QN_OK;
+// workspace: weight digit planes | {scale, bias} pairs | chain flags | two activation digit buffers
+struct I8LayersLayout { size_t Wd, sb, flags, ad[2], total; };
+I8LayersLayout i8_layers_layout(const I8Net& net, int B, int Nb) {
+    int hmax = 0;
+    for (int li = 0; li <= net.nl; ++li) hmax = net.h[li] > hmax ? net.h[li] : hmax;
+    qn_ws_carver c;
+    I8LayersLayout w;
+    w.Wd = c.take((size_t)B * net.dbytes);
+    w.sb = c.take<double>((size_t)B * net.sdoubles);
+    w.flags = c.take<int>((size_t)B);
+    for (size_t& ad : w.ad) ad = c.take((size_t)B * NS * Nb * hmax);
+    w.total = c.total;
+    return w;
 }
 }  // namespace
 
@@ -956,14 +954,9 @@ bool qn_i8_layers_apply(const qn_desc* d) {
     I8Net net;
     return i8net_of(d, &net);
 }
-// bytes of: weight digit planes | {scale, bias} pairs | chain flags | two activation digit buffers
 size_t qn_i8_layers_workspace(const qn_desc* d, int B, int Nb) {
     I8Net net;
-    if (!i8net_of(d, &net)) return 0;
-    int hmax = 0;
-    for (int li = 0; li <= net.nl; ++li) hmax = net.h[li] > hmax ? net.h[li] : hmax;
-    return qn_align((size_t)B * net.dbytes) + qn_align((size_t)B * net.sdoubles * sizeof(double)) + qn_align((size_t)B * sizeof(int)) +
-           2 * qn_align((size_t)B * NS * Nb * hmax);
+    return i8net_of(d, &net) ? i8_layers_layout(net, B, Nb).total : 0;
 }
 // forward through the first layer and every hidden->hidden layer: act[l] (float64 [B][dims[l+1]][Nb], l = 0 .. L-2) are
 // written as the float64 layer-wise kernels would write them
@@ -971,18 +964,11 @@ int qn_i8_layers_forward(const qn_desc* d, const double* W, const double* X, con
                          double* const* act, void* ws, hipStream_t st) {
     I8Net net;
     if (!i8net_of(d, &net)) return QN_EUNSUPPORTED;
-    int hmax = 0;
-    for (int li = 0; li <= net.nl; ++li) hmax = net.h[li] > hmax ? net.h[li] : hmax;
-    char* base = static_cast<char*>(ws);
-    unsigned char* Wd = reinterpret_cast<unsigned char*>(base);
-    base += qn_align((size_t)B * net.dbytes);
-    double* sb = reinterpret_cast<double*>(base);
-    base += qn_align((size_t)B * net.sdoubles * sizeof(double));
-    int* flags = reinterpret_cast<int*>(base);
-    base += qn_align((size_t)B * sizeof(int));
-    unsigned char* ad[2];
-    ad[0] = reinterpret_cast<unsigned char*>(base);
-    ad[1] = ad[0] + qn_align((size_t)B * NS * Nb * hmax);
+    const I8LayersLayout lay = i8_layers_layout(net, B, Nb);
+    unsigned char* Wd = qn_ws_at<unsigned char>(ws, lay.Wd);
+    double* sb = qn_ws_at(ws, lay.sb);
+    int* flags = qn_ws_at<int>(ws, lay.flags);
+    unsigned char* ad[2] = {qn_ws_at<unsigned char>(ws, lay.ad[0]), qn_ws_at<unsigned char>(ws, lay.ad[1])};
 #ifndef QN_I8_LMIN
 #define QN_I8_LMIN 4
 #endif
@@ -1008,12 +994,12 @@ int qn_i8_layers_forward(const qn_desc* d, const double* W, const double* X, con
         const unsigned grid = (unsigned)(((g.outer_total + 7) / 8) * 8 * g.mtiles);
         if (g.h_in == 128) {
             auto kern = k_i8_gemm<QN_I8_LMIN, 2>;
-            if (int rc = i8_arm(reinterpret_cast<const void*>(kern), i8gemm_lds(2))) return rc;
+            if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), i8gemm_lds(2))) return rc;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(512), i8gemm_lds(2), st, g, W, Wd, sb, (const unsigned char*)ad[li & 1],
                                (const double*)act[li], flags, act[li + 1], out_digits);
         } else {
             auto kern = k_i8_gemm<QN_I8_LMIN, 4>;
-            if (int rc = i8_arm(reinterpret_cast<const void*>(kern), i8gemm_lds(4))) return rc;
+            if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), i8gemm_lds(4))) return rc;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(512), i8gemm_lds(4), st, g, W, Wd, sb, (const unsigned char*)ad[li & 1],
                                (const double*)act[li], flags, act[li + 1], out_digits);
         }

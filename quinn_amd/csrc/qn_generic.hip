@@ -10,6 +10,7 @@
 // LDS-resident weights.
 #include "qn_common.h"
 #include "qn_fused_args.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include <type_traits>
 #include <algorithm>
@@ -562,49 +563,49 @@ inline int dw_ksplit(int B, int tiles, int Nb, int target = 4096) {
     return ks < 1 ? 1 : ks;
 }
 
-struct Carve {
-    char* base; size_t off, cap;
-    template <typename U> U* take(size_t n) {
-        U* ptr = reinterpret_cast<U*>(base + off);
-        off += qn_align(n * sizeof(U));
-        return ptr;
-    }
+// Workspace of the layer-wise MLP kernels (`e`: bytes of the compute dtype):
+//   act[l] [B][dims[l+1]][Ns], l < L-1: the output of layer l
+//   gradient calls: dz_last [B][o][Nb] | dZ buffers [B][hmax][Ns], equally sized and consecutive: two, or -- the fused int8-slice
+//     backward writes dZ of EVERY hidden layer before the weight-gradient kernels run -- L - 1
+//   SSE partials [B][nblk]
+//   gradient calls: split-K slabs of the MFMA dW GEMM (float64 hidden->hidden layers with widths % 64 == 0)
+//   float64: workspace of the layer-wise int8-slice forward | of the fused int8-slice kernels (whichever applies)
+// Ns, the row stride of the activation / dZ stashes: the gradient of the wide int8 path (qn_wide_i8.hip, qn_dw_i8.hip: every
+// kernel that touches them takes the stride) pads it to a multiple of 16 rows: a feature's rows then start on a 128-byte line
+// whatever the row count -- an unpadded odd count cost those kernels ~12 %, one that is not a multiple of 16 ~5 %
+// (profiles/r04_ragged_rows_dw_ab.txt).  A run pads from 64 rows on, where the hidden matrices' weight gradient is the int8
+// kernel's, and only on QN_PATH_AUTO; the size query (`sizing`) allows for the padding whatever path the descriptor is forced
+// to and at any row count.
+struct GenericLayout {
+    int Ns;
+    size_t act[QN_MAX_LAYERS], partial, total;
+    size_t dz_last = QN_WS_NONE, dzbuf[2] = {QN_WS_NONE, QN_WS_NONE}, dwslab = QN_WS_NONE, i8_ws = QN_WS_NONE, wide_ws = QN_WS_NONE;
 };
-
-template <typename T>
-int run_generic(const qn_desc* d, const T* W, const T* X, const T* Y, const int32_t* row_idx, int B, int N,
-                int Nb, double* sse, T* pred, T* gradW, void* ws, size_t ws_bytes, hipStream_t st) {
+GenericLayout generic_layout(const qn_desc* d, int B, int Nb, bool grad, bool f64, bool sizing) {
     const int L = d->nlayers;
-    const bool grad = gradW != nullptr;
-    (void)hipGetLastError();   // drop any stale error of this thread before our launches
-    Carve c{static_cast<char*>(ws), 0, ws_bytes};
-    // Row stride of the activation / dZ stashes [B][h][Ns].  The gradient of the wide int8 path (qn_wide_i8.hip, qn_dw_i8.hip: every
-    // kernel that touches them takes the stride) pads it to a multiple of 16 rows: a feature's rows then start on a 128-byte line
-    // whatever the row count -- an unpadded odd count cost those kernels ~12 %, one that is not a multiple of 16 ~5 %
-    // (profiles/r04_ragged_rows_dw_ab.txt).  From 64 rows on, where the hidden matrices' weight gradient is the int8 kernel's.
-    int Ns = Nb;
-    if constexpr (std::is_same<T, double>::value) {
-#ifndef QN_NO_STASH_PAD
-        if (grad && Nb >= 64 && d->path == QN_PATH_AUTO && qn_i8_wide_applies(d)) Ns = wide_stash_stride(Nb);
+    const size_t e = f64 ? 8 : 4;
+    const bool wide_f64 = f64 && qn_i8_wide_applies(d);
+    bool pad = grad && wide_f64;
+    if (!sizing) {
+#ifdef QN_NO_STASH_PAD
+        pad = false;
+#else
+        pad = pad && Nb >= 64 && d->path == QN_PATH_AUTO;
 #endif
     }
-    std::vector<T*> act(L, nullptr);            // act[l] = output of layer l (l < L-1)
-    for (int l = 0; l + 1 < L; ++l) act[l] = c.take<T>((size_t)B * d->dims[l + 1] * Ns);
-    T* dz_last = grad ? c.take<T>((size_t)B * d->dims[L] * Nb) : nullptr;
-    T* dzbuf[2] = {nullptr, nullptr};
-    if (grad && L > 1) {
-        dzbuf[0] = c.take<T>((size_t)B * d->hmax * Ns);
-        dzbuf[1] = c.take<T>((size_t)B * d->hmax * Ns);
-        // the fused int8-slice backward writes dZ of EVERY hidden layer before the weight-gradient kernels run: L - 1
-        // consecutive buffers, the two above being the first
-        if constexpr (std::is_same<T, double>::value)
-            if (qn_i8_wide_applies(d))
-                for (int l = 2; l < L - 1; ++l) c.take<T>((size_t)B * d->hmax * Ns);
+    qn_ws_carver c;
+    GenericLayout w;
+    w.Ns = pad ? wide_stash_stride(Nb) : Nb;
+    for (int l = 0; l + 1 < L; ++l) w.act[l] = c.take((size_t)B * d->dims[l + 1] * w.Ns * e);
+    if (grad) {
+        w.dz_last = c.take((size_t)B * d->dims[L] * Nb * e);
+        const int ndz = L > 1 ? (wide_f64 ? L - 1 : 2) : 0;      // (wide networks have L >= 3)
+        for (int k = 0; k < ndz; ++k) {
+            const size_t off = c.take((size_t)B * d->hmax * w.Ns * e);
+            if (k < 2) w.dzbuf[k] = off;
+        }
     }
-    const int nblk = (Nb + BLK - 1) / BLK;
-    double* partial = c.take<double>((size_t)B * nblk);
-    // split-K slabs of the MFMA dW GEMM (float64 hidden->hidden layers with widths % 64 == 0)
-    T* dwslab = nullptr;
+    w.partial = c.take<double>((size_t)B * ((Nb + BLK - 1) / BLK));
     if (grad) {
         size_t need = 0;
         for (int l = 1; l + 1 < L; ++l)
@@ -613,30 +614,49 @@ int run_generic(const qn_desc* d, const T* W, const T* X, const T* Y, const int3
                 const int ks = dw_ksplit(B, tiles, Nb);          // (the larger of the two targets: an upper bound for the int8 path)
                 if (ks > 1) need = std::max(need, (size_t)B * ks * ((size_t)d->dims[l] * d->dims[l + 1] + d->dims[l + 1]));
             }
-        if (need) dwslab = c.take<T>(need);
+        if (need) w.dwslab = c.take(need * e);
     }
+    const size_t nb8 = f64 && !wide_f64 ? qn_i8_layers_workspace(d, B, Nb) : 0;      // (0 if it does not apply; the fused kernels take precedence)
+    if (nb8) w.i8_ws = c.take(nb8);
+    const size_t nbw = f64 ? qn_i8_wide_workspace(d, B, Nb, grad) : 0;               // (0 if it does not apply)
+    if (nbw) w.wide_ws = c.take(nbw);
+    w.total = c.total;
+    return w;
+}
+
+template <typename T>
+int run_generic(const qn_desc* d, const T* W, const T* X, const T* Y, const int32_t* row_idx, int B, int N,
+                int Nb, double* sse, T* pred, T* gradW, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int L = d->nlayers;
+    const bool grad = gradW != nullptr;
+    (void)hipGetLastError();   // drop any stale error of this thread before our launches
+    const GenericLayout lay = generic_layout(d, B, Nb, grad, std::is_same<T, double>::value, false);
+    if (lay.total > ws_bytes) {
+        qn_set_error("workspace too small: need %zu bytes, got %zu", lay.total, ws_bytes);
+        return QN_EWORKSPACE;
+    }
+    const int Ns = lay.Ns;
+    std::vector<T*> act(L, nullptr);            // act[l] = output of layer l (l < L-1)
+    for (int l = 0; l + 1 < L; ++l) act[l] = qn_ws_at<T>(ws, lay.act[l]);
+    T* dz_last = qn_ws_at<T>(ws, lay.dz_last);
+    T* dzbuf[2] = {qn_ws_at<T>(ws, lay.dzbuf[0]), qn_ws_at<T>(ws, lay.dzbuf[1])};
+    const int nblk = (Nb + BLK - 1) / BLK;
+    double* partial = qn_ws_at(ws, lay.partial);
+    T* dwslab = qn_ws_at<T>(ws, lay.dwslab);
+    void* i8_ws = qn_ws_at<char>(ws, lay.i8_ws);
+    void* wide_ws = qn_ws_at<char>(ws, lay.wide_ws);
     // float64 tanh networks whose hidden widths are multiples of 64: the first layer and the hidden->hidden layers of
     // the FORWARD pass run as sliced int8 products (qn_fused_i8.hip: qn_i8_layers_forward), unless a kernel family is
     // forced on the descriptor (QN_PATH_GENERIC stays the exact float64 reference of the tests)
     bool i8_fwd = false, wide = false;
-    void* i8_ws = nullptr;
-    void* wide_ws = nullptr;
     if constexpr (std::is_same<T, double>::value) {
 #ifndef QN_NO_I8_LAYERS
         i8_fwd = d->path == QN_PATH_AUTO && qn_i8_layers_apply(d);
 #endif
-        const size_t nb8 = qn_i8_wide_applies(d) ? 0 : qn_i8_layers_workspace(d, B, Nb);      // (the fused kernels take precedence)
-        if (nb8) i8_ws = c.take<char>(nb8);
 #ifndef QN_NO_I8_WIDE
         // uniform 128 / 256-wide networks with one output: the whole forward pass is ONE launch (qn_wide_i8.hip)
         wide = d->path == QN_PATH_AUTO && qn_i8_wide_applies(d);
 #endif
-        const size_t nbw = qn_i8_wide_workspace(d, B, Nb, grad);
-        if (nbw) wide_ws = c.take<char>(nbw);
-    }
-    if (c.off > ws_bytes) {
-        qn_set_error("workspace too small: need %zu bytes, got %zu", c.off, ws_bytes);
-        return QN_EWORKSPACE;
     }
     constexpr int JB = 8;
     auto largs = [&](int l) {
@@ -689,7 +709,7 @@ int run_generic(const qn_desc* d, const T* W, const T* X, const T* Y, const int3
         // fused int8-slice backward through the hidden layers (qn_wide_i8.hip): dZ_l of every hidden layer in one launch
         bool wide_bwd = false;
         int last_done = 0;                                   // the output layer's weight gradient came out of the fused backward (h = 128)
-        const int64_t dz_stride = (int64_t)(qn_align((size_t)B * d->hmax * Ns * sizeof(T)) / sizeof(T));
+        const int64_t dz_stride = dzbuf[1] - dzbuf[0];       // (the layout's dZ buffers are consecutive and equally sized)
         if constexpr (std::is_same<T, double>::value) {
 #ifndef QN_NO_I8_WIDE_BWD
             wide_bwd = wide;
@@ -866,6 +886,35 @@ __global__ __launch_bounds__(BLK) void k_rn_add(const T* __restrict__ g, int64_t
     if (e < n) t[e] += g[e];
 }
 
+// Workspace of the layer-wise residual-network kernels (`e`: bytes of the compute dtype), nact = B * r * Nb elements:
+//   OUT_0 | per step TH_i (| OUT_{i+1}, unless mlp: then it IS TH_i) | Weff [B][S][r r + r] | identity [r][r] | SSE partials
+//   gradient calls: dz_last [B][o][Nb] | three scratch buffers of nact | dWeff
+struct RnetLayout {
+    size_t OUT[QN_MAX_LAYERS + 1], TH[QN_MAX_LAYERS], Weff, eye, partial, total;
+    size_t dz_last = QN_WS_NONE, buf[3] = {QN_WS_NONE, QN_WS_NONE, QN_WS_NONE}, dWeff = QN_WS_NONE;
+};
+RnetLayout rnet_layout(const qn_desc* d, int B, int Nb, bool grad, size_t e) {
+    const int r = d->rn_r, S = d->rn_steps;
+    const size_t nact = (size_t)B * r * Nb * e, weff = (size_t)B * S * (r * r + r) * e;
+    qn_ws_carver c;
+    RnetLayout w;
+    w.OUT[0] = c.take(nact);
+    for (int i = 0; i < S; ++i) {
+        w.TH[i] = c.take(nact);
+        w.OUT[i + 1] = d->rn_mlp ? w.TH[i] : c.take(nact);
+    }
+    w.Weff = c.take(weff);
+    w.eye = c.take((size_t)r * r * e);
+    w.partial = c.take<double>((size_t)B * ((Nb + BLK - 1) / BLK));
+    if (grad) {
+        w.dz_last = c.take((size_t)B * d->dims[2] * Nb * e);
+        for (size_t& b : w.buf) b = c.take(nact);
+        w.dWeff = c.take(weff);
+    }
+    w.total = c.total;
+    return w;
+}
+
 template <typename T>
 int run_rnet(const qn_desc* d, const T* W, const T* X, const T* Y, const int32_t* row_idx, int B, int N, int Nb,
              double* sse, T* pred, T* gradW, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -875,27 +924,21 @@ int run_rnet(const qn_desc* d, const T* W, const T* X, const T* Y, const int32_t
     const int per = r * r + r;
     const int64_t nact = (int64_t)B * r * Nb;
     (void)hipGetLastError();
-    Carve c{static_cast<char*>(ws), 0, ws_bytes};
-    std::vector<T*> OUT(S + 1), TH(S);
-    OUT[0] = c.take<T>(nact);
-    for (int i = 0; i < S; ++i) {
-        TH[i] = c.take<T>(nact);
-        OUT[i + 1] = d->rn_mlp ? TH[i] : c.take<T>(nact);
-    }
-    T* Weff = c.take<T>((size_t)B * S * per);
-    T* eye = c.take<T>((size_t)r * r);
-    const int nblk = (Nb + BLK - 1) / BLK;
-    double* partial = c.take<double>((size_t)B * nblk);
-    T *dz_last = nullptr, *dWeff = nullptr, *buf[3] = {nullptr, nullptr, nullptr};
-    if (grad) {
-        dz_last = c.take<T>((size_t)B * o * Nb);
-        for (int i = 0; i < 3; ++i) buf[i] = c.take<T>(nact);
-        dWeff = c.take<T>((size_t)B * S * per);
-    }
-    if (c.off > ws_bytes) {
-        qn_set_error("workspace too small: need %zu bytes, got %zu", c.off, ws_bytes);
+    const RnetLayout lay = rnet_layout(d, B, Nb, grad, sizeof(T));
+    if (lay.total > ws_bytes) {
+        qn_set_error("workspace too small: need %zu bytes, got %zu", lay.total, ws_bytes);
         return QN_EWORKSPACE;
     }
+    std::vector<T*> OUT(S + 1), TH(S);
+    for (int i = 0; i <= S; ++i) OUT[i] = qn_ws_at<T>(ws, lay.OUT[i]);
+    for (int i = 0; i < S; ++i) TH[i] = qn_ws_at<T>(ws, lay.TH[i]);
+    T* Weff = qn_ws_at<T>(ws, lay.Weff);
+    T* eye = qn_ws_at<T>(ws, lay.eye);
+    const int nblk = (Nb + BLK - 1) / BLK;
+    double* partial = qn_ws_at(ws, lay.partial);
+    T* dz_last = qn_ws_at<T>(ws, lay.dz_last);
+    T* dWeff = qn_ws_at<T>(ws, lay.dWeff);
+    T* buf[3] = {qn_ws_at<T>(ws, lay.buf[0]), qn_ws_at<T>(ws, lay.buf[1]), qn_ws_at<T>(ws, lay.buf[2])};
     RnCoef cf;
     for (int i = 0; i < S * d->rn_npar; ++i) cf.c[i] = d->rn_coef[i];
     for (int i = 0; i < S * d->rn_npar; ++i) cf.use[i] = d->rn_uses[i];
@@ -986,32 +1029,7 @@ int run_rnet(const qn_desc* d, const T* W, const T* X, const T* Y, const int32_t
 }  // namespace
 
 size_t qn_generic_workspace(const qn_desc* d, int B, int Nb, int want_grad, int dtype) {
-    const size_t e = dtype == QN_F64 ? 8 : 4;
-    const int L = d->nlayers;
-    size_t tot = 0;
-    // (the wide int8 gradient path pads the stashes' row stride: sized for it whatever path the descriptor is forced to)
-    const int Ns = (dtype == QN_F64 && want_grad && qn_i8_wide_applies(d)) ? wide_stash_stride(Nb) : Nb;
-    for (int l = 0; l + 1 < L; ++l) tot += qn_align((size_t)B * d->dims[l + 1] * Ns * e);
-    if (want_grad) {
-        tot += qn_align((size_t)B * d->dims[L] * Nb * e);
-        if (L > 1) tot += 2 * qn_align((size_t)B * d->hmax * Ns * e);
-        if (dtype == QN_F64 && qn_i8_wide_applies(d))
-            for (int l = 2; l < L - 1; ++l) tot += qn_align((size_t)B * d->hmax * Ns * e);
-    }
-    tot += qn_align((size_t)B * ((Nb + BLK - 1) / BLK) * sizeof(double));
-    if (want_grad) {
-        size_t need = 0;
-        for (int l = 1; l + 1 < L; ++l)
-            if (gemm_layer(d, l)) {
-                const int tiles = (d->dims[l] / 64) * (d->dims[l + 1] / 64);
-                const int ks = dw_ksplit(B, tiles, Nb);
-                if (ks > 1) need = std::max(need, (size_t)B * ks * ((size_t)d->dims[l] * d->dims[l + 1] + d->dims[l + 1]));
-            }
-        tot += qn_align(need * e);
-    }
-    if (dtype == QN_F64 && !qn_i8_wide_applies(d)) tot += qn_align(qn_i8_layers_workspace(d, B, Nb));      // layer-wise int8-slice forward (0 if it does not apply)
-    if (dtype == QN_F64) tot += qn_align(qn_i8_wide_workspace(d, B, Nb, want_grad));        // fused int8-slice forward (0 if it does not apply)
-    return tot + 256;
+    return generic_layout(d, B, Nb, want_grad != 0, dtype == QN_F64, true).total + 256;
 }
 
 int qn_generic_run(const qn_desc* d, int dtype, const void* W, const void* X, const void* Y,
@@ -1025,14 +1043,7 @@ int qn_generic_run(const qn_desc* d, int dtype, const void* W, const void* X, co
 }
 
 size_t qn_rnet_workspace(const qn_desc* d, int B, int Nb, int want_grad, int dtype) {
-    const size_t e = dtype == QN_F64 ? 8 : 4;
-    const int r = d->rn_r, S = d->rn_steps, o = d->dims[2];
-    const size_t nact = qn_align((size_t)B * r * Nb * e);
-    const size_t weff = qn_align((size_t)B * S * (r * r + r) * e);
-    size_t tot = nact * (1 + (d->rn_mlp ? S : 2 * S)) + weff + qn_align((size_t)r * r * e);
-    tot += qn_align((size_t)B * ((Nb + BLK - 1) / BLK) * sizeof(double));
-    if (want_grad) tot += qn_align((size_t)B * o * Nb * e) + 3 * nact + weff;
-    return tot + 256;
+    return rnet_layout(d, B, Nb, want_grad != 0, dtype == QN_F64 ? 8 : 4).total + 256;
 }
 
 int qn_rnet_run(const qn_desc* d, int dtype, const void* W, const void* X, const void* Y, const int32_t* row_idx,

@@ -14,6 +14,7 @@
 // Threads per block are chosen so that stash + accumulators fit LDS (256 / 128 / 64); networks that do not fit
 // fall back to the layer-wise path.  float64 only.  Bound: the DP VALU (tanh) -- per row ~S*R tanh and 2 S R^2 flops.
 #include "qn_common.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include <algorithm>
 
@@ -441,47 +442,42 @@ int blocks_for(int B, int Nb, int T) {
     return nb < 1 ? 1 : nb;
 }
 
+// workspace: SSE partials [B][nblk] | gradient calls: slabs [B][nblk][nimg] (nimg = img_doubles<R>(S))
+struct RnFusedLayout { size_t partial, slab = QN_WS_NONE, total; };
+RnFusedLayout rnet_fused_layout(int B, int nblk, int nimg, bool grad) {
+    qn_ws_carver c;
+    RnFusedLayout w;
+    w.partial = c.take<double>((size_t)B * nblk);
+    if (grad) w.slab = c.take<double>((size_t)B * nblk * nimg);
+    w.total = c.total;
+    return w;
+}
+
 template <int R>
 int run(const qn_desc* d, RnFusedArgs& a, const double* W, const double* X, const double* Y, const int32_t* row_idx,
         double* sse, double* pred, double* gradW, void* ws, size_t ws_bytes, hipStream_t st) {
     const bool grad = gradW != nullptr;
     a.T = grad ? pick_T<R>(a.S, a.r) : 256;
     a.nblk = blocks_for(a.B, a.Nb, a.T);
-    const size_t npart = qn_align((size_t)a.B * a.nblk * sizeof(double));
-    const size_t nslab = grad ? qn_align((size_t)a.B * a.nblk * img_doubles<R>(a.S) * sizeof(double)) : 0;
-    if (npart + nslab > ws_bytes) {
-        qn_set_error("workspace too small: need %zu bytes, got %zu", npart + nslab, ws_bytes);
+    const RnFusedLayout lay = rnet_fused_layout(a.B, a.nblk, img_doubles<R>(a.S), grad);
+    if (lay.total > ws_bytes) {
+        qn_set_error("workspace too small: need %zu bytes, got %zu", lay.total, ws_bytes);
         return QN_EWORKSPACE;
     }
-    double* partial = static_cast<double*>(ws);
-    double* slab = reinterpret_cast<double*>(static_cast<char*>(ws) + npart);
+    double* partial = qn_ws_at(ws, lay.partial);
+    double* slab = qn_ws_at(ws, lay.slab);
     (void)hipGetLastError();
     if (!grad && (a.d > DOMAX || a.o > DOMAX)) {
-        static bool armed = false;
-        if (!armed) {
-            QN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rnet_fwd<R, DOWIDE>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            armed = true;
-        }
         const size_t lds_w = fwd_lds<R, DOWIDE>(a.S);
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(k_rnet_fwd<R, DOWIDE>), lds_w)) return rc;
         hipLaunchKernelGGL((k_rnet_fwd<R, DOWIDE>), dim3(a.nblk, a.B), dim3(256), lds_w, st, a, W, X, Y, row_idx, pred,
                            partial);
     } else if (!grad) {
-        static bool armed = false;
-        if (!armed) {
-            QN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rnet_fwd<R>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            armed = true;
-        }
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(k_rnet_fwd<R>), fwd_lds<R>(a.S))) return rc;
         hipLaunchKernelGGL(k_rnet_fwd<R>, dim3(a.nblk, a.B), dim3(256), fwd_lds<R>(a.S), st, a, W, X, Y, row_idx, pred,
                            partial);
     } else {
-        static bool armed = false;
-        if (!armed) {
-            QN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rnet_bwd<R>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            armed = true;
-        }
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(k_rnet_bwd<R>), bwd_lds<R>(a.S, a.T, a.r))) return rc;
         hipLaunchKernelGGL(k_rnet_bwd<R>, dim3(a.nblk, a.B), dim3(a.T), bwd_lds<R>(a.S, a.T, a.r), st, a, W, X, Y, row_idx, pred,
                            partial, slab);
         int gx = (int)((a.p + 255) / 256);
@@ -509,7 +505,7 @@ size_t qn_rnet_fused_workspace(const qn_desc* d, int B, int Nb, int want_grad) {
     const int T = want_grad ? (R == 4 ? pick_T<4>(d->rn_steps, d->rn_r) : pick_T<8>(d->rn_steps, d->rn_r)) : 256;
     const int nblk = blocks_for(B, Nb, T ? T : 256);
     const int nimg = R == 4 ? img_doubles<4>(d->rn_steps) : img_doubles<8>(d->rn_steps);
-    return qn_align((size_t)B * nblk * sizeof(double)) + (want_grad ? qn_align((size_t)B * nblk * nimg * sizeof(double)) : 0) + 256;
+    return rnet_fused_layout(B, nblk, nimg, want_grad != 0).total + 256;
 }
 
 int qn_rnet_fused_run(const qn_desc* d, const void* W, const void* X, const void* Y, const int32_t* row_idx, int B, int N,

@@ -22,11 +22,10 @@
 // with an unbounded input, take a plain float64 loop (IEEE semantics of the layer-wise kernels).
 #include "qn_common.h"
 #include "qn_fused_args.h"
+#include "qn_host_args.h"
 #include "qn_math.h"
 #include "qn_i8_slice.h"
 #include <cstring>
-#include <mutex>
-#include <unordered_set>
 
 // This file is compiled as TWO objects so that its ~40 kernel instances build in parallel: part 0 (this file) holds everything but the
 // relu / identity forward instances, part 1 (qn_wide_u_i8.hip: `#define QN_WIDE_PART 1` + `#include` of this file) holds those and
@@ -1325,39 +1324,6 @@ __global__ void k_wide_sum(const double* __restrict__ partial, int nsplit, int B
     sse[b] = s;
 }
 
-void wide_plan(int B, int Nb, WideArgs* a) {
-    const int rows_it = 64, target = 256;                // one workgroup per CU
-    const int max_split = (Nb + rows_it - 1) / rows_it;
-    int nsplit = (target + B - 1) / B;
-    if (nsplit > max_split) nsplit = max_split;
-    if (nsplit < 1) nsplit = 1;
-    int rps = (Nb + nsplit - 1) / nsplit;
-    rps = (rps + rows_it - 1) / rows_it * rows_it;
-    a->nsplit = (Nb + rps - 1) / rps;
-    a->rows_per_split = rps;
-    a->iters = rps / rows_it;
-}
-
-// Raise a kernel's dynamic-LDS limit ONCE per (kernel, device) to the hardware maximum: the bytes a launch asks for grow with
-// the number of hidden layers while the kernel templates do not depend on it (arming with the first caller's size left a
-// later, deeper network above the limit), and the attribute is per device.
-int wide_arm(const void* fn, size_t bytes) {
-    static std::mutex mu;
-    static std::unordered_set<uint64_t> armed;
-    if (bytes > 160 * 1024) {
-        qn_set_error("int8-slice kernel needs %zu bytes of LDS (limit 160 KB)", bytes);
-        return QN_EUNSUPPORTED;
-    }
-    int dev = 0;
-    QN_HIP_CHECK(hipGetDevice(&dev));
-    const uint64_t key = (uint64_t)(uintptr_t)fn * 64u + (uint64_t)(dev & 63);
-    std::lock_guard<std::mutex> lock(mu);
-    if (armed.count(key)) return QN_OK;
-    QN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    armed.insert(key);
-    return QN_OK;
-}
-
 }  // namespace
 
 // columns of the first layer's LDS image / registers of a row's inputs: 2, 4 or (5..8 inputs: round 4) 8
@@ -1383,7 +1349,7 @@ int qn_i8_wide_launch_u(int h, int dp, int stash, size_t lds, unsigned grid, hip
     else
         ku = h == 128 ? (dp == 2 ? k_i8_wide_fwd_u<2, 2, QN_I8_LMIN, false> : dp == 4 ? k_i8_wide_fwd_u<2, 4, QN_I8_LMIN, false> : k_i8_wide_fwd_u<2, 8, QN_I8_LMIN, false>)
                       : (dp == 2 ? k_i8_wide_fwd_u<4, 2, QN_I8_LMIN, false> : dp == 4 ? k_i8_wide_fwd_u<4, 4, QN_I8_LMIN, false> : k_i8_wide_fwd_u<4, 8, QN_I8_LMIN, false>);
-    if (int rc = wide_arm(reinterpret_cast<const void*>(ku), lds)) return rc;
+    if (int rc = qn_arm_lds(reinterpret_cast<const void*>(ku), lds)) return rc;
     hipLaunchKernelGGL(ku, dim3(grid), dim3(WWG), lds, st, a, W, X, Y, row_idx, Wd, sb, flags, act0, dz_last, pred, partial, dump, act,
                        rowsc, rs_stride);
     return QN_OK;
@@ -1404,29 +1370,57 @@ bool qn_i8_wide_applies(const qn_desc* d) {
         if (d->dims[l] != h) return false;
     return wide_lds_bytes(h / 64, wide_dp(d->dims[0]), L - 1) <= 160 * 1024 && wideb_lds_bytes(h / 64, L - 1) <= 160 * 1024;
 }
-// bytes of: weight digit planes | {scale, bias} pairs | chain flags | SSE partials | dump area of the activation stash
-size_t qn_i8_wide_workspace(const qn_desc* d, int B, int Nb, int want_grad) {
-    if (!qn_i8_wide_applies(d)) return 0;
+// one workgroup per CU over the chip, 64 rows per iteration
+static qn_row_split wide_split(int B, int Nb) { return qn_plan_row_split(B, Nb, 64, 256); }
+// the hidden->hidden layers of the (uniform-width) network for the digit-slicing kernels; `sper` doubles per layer and unit in
+// a chain's scale block: 2 = the forward's {scale, bias} pairs, 1 = the scales of the backward's transposed matrices
+static I8Net wide_net(const qn_desc* d, int sper) {
     const int h = d->dims[1], nhh = d->nlayers - 2;
-    WideArgs a;
-    wide_plan(B, Nb, &a);
-    size_t tot = qn_align((size_t)B * nhh * NS * h * h) + qn_align((size_t)B * nhh * 2 * h * sizeof(double)) +
-                 qn_align((size_t)B * sizeof(int)) + qn_align((size_t)B * a.nsplit * sizeof(double)) +
-                 qn_align(((size_t)3 * Nb + 64) * sizeof(double));
-    // backward: digit planes of the transposed matrices | their scales | chain flags
-    // ... | (h = 128) per-split partial sums of the output layer's weight gradient
-    if (want_grad)
-        tot += qn_align((size_t)B * nhh * NS * h * h) + qn_align((size_t)B * nhh * h * sizeof(double)) + qn_align((size_t)B * sizeof(int)) +
-               qn_align((size_t)B * a.nsplit * (h + 1) * sizeof(double));
-    // relu / identity: ... | the forward's per-row activation scales [nhh][B][Nb] for the weight-gradient kernel
-    if (want_grad && d->act != QN_ACT_TANH) tot += qn_align((size_t)nhh * B * Nb * sizeof(double));
-    return tot;
+    I8Net net;
+    net.nl = nhh; net.p = d->p; net.has_bias = d->has_bias;
+    for (int li = 0; li < nhh; ++li) {
+        net.h[li] = h; net.h[li + 1] = h;
+        net.offW[li] = d->offW[li + 1]; net.offB[li] = d->offB[li + 1];
+        net.offD[li] = (int64_t)li * NS * h * h; net.offS[li] = (int64_t)li * sper * h;
+    }
+    net.dbytes = (int64_t)nhh * NS * h * h;
+    net.sdoubles = (int64_t)nhh * sper * h;
+    return net;
+}
+// workspace of one evaluation, the same for its forward and its backward call:
+//   weight digit planes | {scale, bias} pairs | chain flags | SSE partials | dump area of the stashes (both calls)
+//   gradient: digit planes of the transposed matrices | their scales | chain flags | per-split partial sums of the output
+//             layer's weight gradient (h = 128)
+//   relu / identity gradient: the forward's per-row activation scales [nhh][B][Nb] for the weight-gradient kernel
+struct WideLayout {
+    size_t Wd, sb, flags, partial, dump, total;
+    size_t WdT = QN_WS_NONE, scT = QN_WS_NONE, flagsT = QN_WS_NONE, dwl_slab = QN_WS_NONE, rowsc = QN_WS_NONE;
+};
+static WideLayout wide_layout(const qn_desc* d, int B, int Nb, int want_grad) {
+    const int h = d->dims[1], nhh = d->nlayers - 2, nsplit = wide_split(B, Nb).nsplit;
+    qn_ws_carver c;
+    WideLayout w;
+    w.Wd = c.take((size_t)B * nhh * NS * h * h);
+    w.sb = c.take<double>((size_t)B * nhh * 2 * h);
+    w.flags = c.take<int>((size_t)B);
+    w.partial = c.take<double>((size_t)B * nsplit);
+    w.dump = c.take<double>((size_t)3 * Nb + 64);
+    if (want_grad) {
+        w.WdT = c.take((size_t)B * nhh * NS * h * h);
+        w.scT = c.take<double>((size_t)B * nhh * h);
+        w.flagsT = c.take<int>((size_t)B);
+        w.dwl_slab = c.take<double>((size_t)B * nsplit * (h + 1));
+        if (d->act != QN_ACT_TANH) w.rowsc = c.take<double>((size_t)nhh * B * Nb);
+    }
+    w.total = c.total;
+    return w;
+}
+size_t qn_i8_wide_workspace(const qn_desc* d, int B, int Nb, int want_grad) {
+    return qn_i8_wide_applies(d) ? wide_layout(d, B, Nb, want_grad).total : 0;
 }
 double* qn_i8_wide_rowscale(const qn_desc* d, int B, int Nb, int want_grad, void* ws) {
-    if (!ws || !want_grad || !qn_i8_wide_applies(d) || d->act == QN_ACT_TANH) return nullptr;
-    const int nhh = d->nlayers - 2;
-    return reinterpret_cast<double*>(static_cast<char*>(ws) + qn_i8_wide_workspace(d, B, Nb, 1) -
-                                     qn_align((size_t)nhh * B * Nb * sizeof(double)));
+    if (!ws || !qn_i8_wide_applies(d)) return nullptr;
+    return qn_ws_at(ws, wide_layout(d, B, Nb, want_grad).rowsc);
 }
 // One launch: sse [B] (+ pred [B][Nb], dz_last [B][Nb] = 2 (pred - y), hidden activations act0 + l * act_stride
 // [B][h][Nb] for l = 0 .. L-2, each optional)
@@ -1436,27 +1430,16 @@ int qn_i8_wide_forward(const qn_desc* d, const double* W, const double* X, const
     if (act0 && Ns < Nb) return QN_EINVAL;
     if (!qn_i8_wide_applies(d)) return QN_EUNSUPPORTED;
     const int h = d->dims[1], nhh = d->nlayers - 2;
-    I8Net net;
-    net.nl = nhh; net.p = d->p; net.has_bias = d->has_bias;
-    for (int li = 0; li < nhh; ++li) {
-        net.h[li] = h; net.h[li + 1] = h;
-        net.offW[li] = d->offW[li + 1]; net.offB[li] = d->offB[li + 1];
-        net.offD[li] = (int64_t)li * NS * h * h; net.offS[li] = (int64_t)li * 2 * h;
-    }
-    net.dbytes = (int64_t)nhh * NS * h * h;
-    net.sdoubles = (int64_t)nhh * 2 * h;
-    char* base = static_cast<char*>(ws);
-    unsigned char* Wd = reinterpret_cast<unsigned char*>(base);
-    base += qn_align((size_t)B * net.dbytes);
-    double* sb = reinterpret_cast<double*>(base);
-    base += qn_align((size_t)B * net.sdoubles * sizeof(double));
-    int* flags = reinterpret_cast<int*>(base);
-    base += qn_align((size_t)B * sizeof(int));
-    double* partial = reinterpret_cast<double*>(base);
+    const I8Net net = wide_net(d, 2);
+    const WideLayout lay = wide_layout(d, B, Nb, act0 != nullptr);       // (the stashes are written for gradient calls only)
+    unsigned char* Wd = qn_ws_at<unsigned char>(ws, lay.Wd);
+    double* sb = qn_ws_at(ws, lay.sb);
+    int* flags = qn_ws_at<int>(ws, lay.flags);
+    double* partial = qn_ws_at(ws, lay.partial);
+    double* dump = qn_ws_at(ws, lay.dump);
+    const qn_row_split split = wide_split(B, Nb);
     WideArgs a;
-    wide_plan(B, Nb, &a);
-    base += qn_align((size_t)B * a.nsplit * sizeof(double));
-    double* dump = reinterpret_cast<double*>(base);
+    a.nsplit = split.nsplit; a.rows_per_split = split.rows_per_split; a.iters = split.iters;
     a.p = d->p; a.act_stride = act_stride; a.B = B; a.Nb = Nb; a.d = d->dims[0]; a.nhid = d->nlayers - 1;
     a.has_bias = d->has_bias; a.Ns = act0 ? Ns : Nb;
     QN_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)B * sizeof(int), st));
@@ -1475,10 +1458,10 @@ int qn_i8_wide_forward(const qn_desc* d, const double* W, const double* X, const
     if (d->act != QN_ACT_TANH) {                                    // relu / identity: per-row activation scales (qn_wide_u_i8.hip)
         if (int rc = qn_i8_wide_launch_u(h, dp, act0 != nullptr, lds, qn_fused_grid(a.nsplit, B), st, &a, W, X, Y, row_idx,
                                          (const unsigned char*)Wd, (const double*)sb, (const int*)flags, act0, dz_last, pred, partial,
-                                         dump, d->act, act0 ? qn_i8_wide_rowscale(d, B, Nb, 1, ws) : (double*)nullptr, (int64_t)B * Nb))
+                                         dump, d->act, qn_ws_at(ws, lay.rowsc), (int64_t)B * Nb))
             return rc;
     } else {
-        if (int rc = wide_arm(reinterpret_cast<const void*>(kern), lds)) return rc;
+        if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
         hipLaunchKernelGGL(kern, dim3(qn_fused_grid(a.nsplit, B)), dim3(WWG), lds, st, a, W, X, Y, row_idx,
                            (const unsigned char*)Wd, (const double*)sb, (const int*)flags, act0, dz_last, pred, partial, dump);
     }
@@ -1499,29 +1482,14 @@ int qn_i8_wide_backward(const qn_desc* d, const double* W, const double* X, cons
     if (Ns < Nb) return QN_EINVAL;
     if (!qn_i8_wide_applies(d)) return QN_EUNSUPPORTED;
     const int h = d->dims[1], nhh = d->nlayers - 2;
-    I8Net net;
-    net.nl = nhh; net.p = d->p; net.has_bias = d->has_bias;
-    for (int li = 0; li < nhh; ++li) {
-        net.h[li] = h; net.h[li + 1] = h;
-        net.offW[li] = d->offW[li + 1]; net.offB[li] = d->offB[li + 1];
-        net.offD[li] = (int64_t)li * NS * h * h; net.offS[li] = (int64_t)li * h;
-    }
-    net.dbytes = (int64_t)nhh * NS * h * h;
-    net.sdoubles = (int64_t)nhh * h;
-    WideArgs fa;
-    wide_plan(B, Nb, &fa);
-    char* base = static_cast<char*>(ws);
-    base += qn_align((size_t)B * net.dbytes) + qn_align((size_t)B * nhh * 2 * h * sizeof(double)) + qn_align((size_t)B * sizeof(int)) +
-            qn_align((size_t)B * fa.nsplit * sizeof(double));
-    double* dump = reinterpret_cast<double*>(base);
-    base += qn_align(((size_t)3 * Nb + 64) * sizeof(double));
-    unsigned char* WdT = reinterpret_cast<unsigned char*>(base);
-    base += qn_align((size_t)B * net.dbytes);
-    double* scT = reinterpret_cast<double*>(base);
-    base += qn_align((size_t)B * net.sdoubles * sizeof(double));
-    int* flags = reinterpret_cast<int*>(base);
-    base += qn_align((size_t)B * sizeof(int));
-    double* dwl_slab = reinterpret_cast<double*>(base);
+    const I8Net net = wide_net(d, 1);
+    const qn_row_split fa = wide_split(B, Nb);
+    const WideLayout lay = wide_layout(d, B, Nb, 1);
+    double* dump = qn_ws_at(ws, lay.dump);
+    unsigned char* WdT = qn_ws_at<unsigned char>(ws, lay.WdT);
+    double* scT = qn_ws_at(ws, lay.scT);
+    int* flags = qn_ws_at<int>(ws, lay.flagsT);
+    double* dwl_slab = qn_ws_at(ws, lay.dwl_slab);
     const bool fold_last = (h == 128 || QN_WIDE_FOLD_ALL) && gradW != nullptr && last_done != nullptr;
     WideBwdArgs a;
     a.p = d->p; a.act_stride = act_stride; a.dz_stride = dz_stride; a.B = B; a.Nb = Nb; a.Ns = Ns; a.d = d->dims[0];
@@ -1540,7 +1508,7 @@ int qn_i8_wide_backward(const qn_desc* d, const double* W, const double* X, cons
     else
         kern = h == 128 ? (dp == 2 ? k_i8_wide_bwd<2, 2, QN_I8_LMIN, false> : k_i8_wide_bwd<2, 4, QN_I8_LMIN, false>)
                         : (dp == 2 ? k_i8_wide_bwd<4, 2, QN_I8_LMIN, false> : k_i8_wide_bwd<4, 4, QN_I8_LMIN, false>);
-    if (int rc = wide_arm(reinterpret_cast<const void*>(kern), lds)) return rc;
+    if (int rc = qn_arm_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(qn_fused_grid(a.nsplit, B)), dim3(WWG), lds, st, a, W, X, row_idx, (const unsigned char*)WdT,
                        (const double*)scT, (const int*)flags, act0, dz_last, dz0, dump, fold_last ? dwl_slab : (double*)nullptr,
                        d->act);

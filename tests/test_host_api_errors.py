@@ -3,6 +3,8 @@ QN_EINVAL / QN_EUNSUPPORTED and a message before any HIP call), descriptor life 
 the host-side AddressSanitizer run (tools/asan_host.sh builds the library with the HOST code instrumented and runs this
 file and test_abi_exports.py under it; GPU sanitizers are not available on this pool)."""
 import ctypes
+import json
+import os
 
 import pytest
 
@@ -107,3 +109,32 @@ def test_compute_entry_points_reject_bad_arguments(L):
     assert L.qn_pred_moments(None, 0, 5, 10, one, None, None) == EINVAL
     assert L.qn_debug_tanh(None, one, 4, None) != 0
     assert L.qn_mlp_desc_destroy(d) == 0
+
+
+def test_sse_workspace_sizes_unchanged(L):
+    """qn_workspace_bytes (forward and gradient) and qn_mlp_sse_parts return what tests/golden/g18_sse_workspace_bytes.json
+    records for one network per kernel family of the core operator: the numbers of the library before each family's size query
+    and run function took their offsets from one layout function (gen_golden_sse_ws_sizes.py).  Every network still reaches
+    the family it is there for."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    from gen_golden_sse_ws_sizes import NETS, make_desc, family
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g18_sse_workspace_bytes.json")) as f:
+        rec = json.load(f)
+    assert rec["nets"] == NETS and len(NETS) == 12 and len(rec["cases"]) == 12 * 2 * 2 * 2 * 3 * 5
+    assert {tuple(n["family"][0]) for n in NETS.values()} == {(2, 0), (2, 1), (1, 0), (1, 2), (1, 3)}
+    descs = {name: make_desc(L, net) for name, net in NETS.items()}
+    for name, net in NETS.items():
+        assert family(L, descs[name]) == net["family"], name
+    seen = set()
+    for c in rec["cases"]:
+        h = descs[c["net"]]
+        L.qn_mlp_desc_set_plan_batch(h, c["plan"])
+        L.qn_mlp_desc_set_path(h, c["path"])
+        assert min(c["bytes"]) > 0
+        assert [L.qn_workspace_bytes(h, c["B"], c["rows"], g, c["dtype"]) for g in (0, 1)] == c["bytes"], c
+        assert L.qn_mlp_sse_parts(h, c["B"], c["rows"], c["dtype"]) == c["parts"], c
+        seen.add((c["net"], c["plan"], c["path"], c["dtype"], c["B"], c["rows"]))
+    assert len(seen) == len(rec["cases"])
+    for h in descs.values():
+        L.qn_mlp_desc_destroy(h)
