@@ -323,6 +323,39 @@ int qn_hmc_adapt(const double* cur, const double* alphas, int nmcmc, const int64
                  int m, double target_accept, int collect, int finish, int freeze, int n, double* da, double* eps,
                  double* mean, double* m2, double* scale, void* stream);
 
+/* Stochastic-gradient MCMC on the device (SGLD, SGHMC, optional cyclical step size; build-only, the reference has no such
+ * sampler).  A step is qn_mlp_sse_fwdbwd on each chain's own n_batch rows followed by ONE qn_sg_step; nothing is read back.
+ * Philox4x32-10 keyed by (seed, stream = inner step t, counter = [GLOBAL chain id = chain0 + c : 24][purpose : 4][index : 36]),
+ * purpose 4 = minibatch rows (index = entry / 4), purpose 5 = step noise (index = element pair).
+ *
+ * qn_sg_rows: rows [C, Nb] int32 of inner step t = (step_ptr ? *step_ptr : 0) + step_off: entry j of chain c is
+ *   __umulhi(r, N) in [0, N) with r = word (j & 3) of the block with index j >> 2 -- independent uniform draws WITH
+ *   replacement, pure integer arithmetic (quinn_amd.mcmc.sgmcmc.minibatch_rows restates it bit for bit).
+ * qn_sg_step: reads the inner step t from slot `parity` of step_ptr [2] and, for every chain,
+ *     g   = (n_rows / n_batch) * grad / (2 sigma^2)         grad [C, p] = d SSE / d W of the minibatch, dtype QN_F64 / QN_F32
+ *     eta = eta0                                            schedule 0 (constant)
+ *           eta0 / 2 * (cos(pi (t mod K) / K) + 1)          schedule 1 (cyclic), K = cycle_len >= 2 inner steps per cycle
+ *     on  = 1 (constant);  (t mod K) / K >= explore_frac (cyclic)
+ *     v <- (1 - alpha) v - eta g + on sqrt(2 alpha eta temperature) z,  z ~ N(0, I);   theta <- theta + v
+ *   theta, v: [C, p] float64, updated in place; alpha = 1 (SGLD) never touches v (NULL allowed); temperature = 0 or on = 0:
+ *   no noise is drawn.  theta_op (optional, QN_F32 only): the new positions as float32 [C, p], what a float32 operator's
+ *   next gradient call reads.  In the same launch:
+ *   - t % thin == 0: lps[c, t / thin] = -((n_rows / n_batch) sse[c] / (2 sigma^2) + (n_rows / 2) log 2 pi + n_rows log sigma),
+ *     the MINIBATCH estimate of the log-posterior of the incoming state theta_t (sse [C]: the SSE the gradient call returned);
+ *     where it is >= best_lp, best [C, p] <- theta_t.  best_lp [2, C] is double-buffered like step_ptr (slot `parity` read,
+ *     slot 1 - parity written).  lps [C, nstore + 1].
+ *   - (t + 1) % thin == 0: chain[c, (t + 1) / thin, :] <- the new theta (chain [C, nstore + 1, p] or NULL; rows beyond nstore
+ *     are never written).
+ *   - rows (optional, [2, C, n_batch] int32): the rows of step t + 1 (qn_sg_rows' formula) go to half 1 - parity.
+ *   - step_ptr[1 - parity] = t + 1.
+ *   final != 0: only the log-posterior trace / best update of theta_t; nothing moves, step_ptr[1 - parity] = t. */
+int qn_sg_rows(int32_t* rows, int C, int Nb, int N, int chain0, uint64_t seed, const int64_t* step_ptr, int64_t step_off,
+               void* stream);
+int qn_sg_step(double* theta, double* v, const void* grad, int dtype, const double* sse, double sigma, int n_rows, int n_batch,
+               double eta0, double alpha, double temperature, int schedule, int64_t cycle_len, double explore_frac, int thin,
+               int final, int C, int chain0, int64_t p, int nstore, uint64_t seed, void* theta_op, double* best, double* best_lp,
+               double* chain, double* lps, int32_t* rows, int64_t* step_ptr, int parity, void* stream);
+
 /* Moments of a predictive ensemble on the device (QUiNNBase.predict_mom_sample, quinn/solvers/quinn.py:75-104):
  * Y [M, K] dtype = M members x K = N * o prediction entries as qn_mlp_sse_fwd writes them ([B, Nb, o] with B = M);
  * mean_out [K], var_out [K] (unbiased, ddof = 1; NULL to skip; needs M >= 2), float64.  The per-output covariance of

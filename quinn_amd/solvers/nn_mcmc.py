@@ -23,12 +23,15 @@ from ..mcmc.mala import MALA
 from ..mcmc.device_amcmc import DeviceAMCMC
 from ..mcmc.device_hmc import DeviceHMC
 from ..mcmc.device_mala import DeviceMALA
+from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
 from ..mcmc import diagnostics as diag
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
 
-DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA}      # fit(engine='device'): sampler -> class
+# fit(engine='device'): sampler -> class
+DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 'sgld': DeviceSGLD, 'sghmc': DeviceSGHMC}
+DEVICE_ONLY = ('sgld', 'sghmc')                  # stochastic-gradient samplers: no host counterpart
 
 
 class NN_MCMC(QUiNNBase):
@@ -130,7 +133,8 @@ class NN_MCMC(QUiNNBase):
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
             datanoise (likelihood sigma), nmcmc, param_ini `(p,)` [or `(C,p)`], sampler
-            ('amcmc' | 'hmc' | 'mala'), sampler_params (dict splatted into the sampler).
+            ('amcmc' | 'hmc' | 'mala'; build-only, engine='device': 'sgld' | 'sghmc'), sampler_params (dict splatted into
+            the sampler).
         Build-only: nchains (C independent chains in lock-step), seeds (C ints; chain c then
             equals a reference run preceded by np.random.seed(seeds[c])).  With nchains=1 and
             seeds=None the global numpy RNG is used, exactly like the reference.
@@ -161,12 +165,21 @@ class NN_MCMC(QUiNNBase):
             so it works with gather_chain='none'; host engines: the numpy chain is uploaded in bounded pieces.  Multi-rank:
             each rank reduces its own chains, the small per-chain statistics follow `gather`.  diag_nburn: rows discarded
             first (None: nmcmc // 2).  False (default): nothing is computed and `self.diagnostics` is None.
+            sampler='sgld' | 'sghmc' (engine='device' only; `quinn_amd.mcmc.device_sgmcmc`): stochastic-gradient Langevin /
+            Hamiltonian dynamics, every chain on its own minibatch drawn on the device.  sampler_params: eta (step size),
+            alpha ('sghmc' only: friction in (0, 1], default 0.1), batch (rows per chain and step, with replacement; None: all
+            rows), thin (every thin-th state is stored: nmcmc stored rows are nmcmc * thin inner steps), schedule
+            ('constant' | 'cyclic'), cycles and explore_frac (cyclic: cosine cycles over the run; the head of each cycle runs
+            without noise), temperature (default 1), use_graph, groups.  There is no accept test ('accrate' and 'alphas' are 1)
+            and 'logpost' is the minibatch estimate of each stored state's log-posterior.
             gtrn `(N, d)` | `(N, o, d)` with gradnoise (sigma_g): observed input gradients as a second Gaussian likelihood
             term, log-posterior -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2)
             - N o d (log sigma_g + log(2 pi) / 2) with gsse = sum (dM/dx - gtrn)^2; engine='host' only (the device engines'
             accept kernels take a bare SSE).
         """
         self.diagnostics = None
+        if sampler in DEVICE_ONLY and engine != 'device':
+            raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host SG sampler)")
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
         ntrn_, outdim = ytrn.shape
         assert xtrn.shape[0] == ntrn_
@@ -218,7 +231,7 @@ class NN_MCMC(QUiNNBase):
             lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
             seed0 = seeds[0] if seeds else 0
             if sampler not in DEVICE_ENGINES:
-                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc' and 'mala'")
+                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld' and 'sghmc'")
             # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
             eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, **sampler_params)
             if hi > lo:
