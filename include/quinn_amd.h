@@ -507,6 +507,41 @@ size_t qn_chain_stats_workspace_bytes(int C, int64_t T, int64_t K, int nbatch, i
 int qn_chain_stats(const void* chain, int dtype, int C, int64_t T, int64_t K, int64_t t0, int nbatch, int64_t blen,
                    double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scores of a predictive ensemble against data (quinn_amd/scoring.py forms the scalar summaries; the reference has no
+ * counterpart, these formulas are the contract).  F [M, K] contiguous, dtype QN_F64 or QN_F32: member m's predictive mean of
+ * entry k -- what qn_mlp_sse_fwd writes as pred_out with B = M, K = N * o.  V [M, K] of the same dtype or NULL: a
+ * per-member predictive variance.  Y [K] float64: the targets, shared by the members.  Member m predicts
+ * N(f_mk, s_mk^2), s_mk^2 = sigma^2 + V_mk, and the predictive is the equal-weight mixture of the members.  With
+ * ll_mk = -0.5 (y_k - f_mk)^2 / s_mk^2 - 0.5 log(2 pi s_mk^2), out [QN_SCORE_NOUT, K] float64 holds per entry:
+ *   row 0  lppd    logsumexp_m ll_mk - log M                                             (QN_SCORE_LPPD)
+ *   row 1  p_waic  variance (ddof = 1) over the members of ll_mk                          (QN_SCORE_PWAIC)
+ *   row 2  pit     (1/M) sum_m Phi((y_k - f_mk) / s_mk); a member with s_mk = 0 counts 1 / 0.5 / 0 for f < y, f == y, f > y
+ *                                                                                        (QN_SCORE_PIT)
+ *   row 3  crps    (1/M) sum_i A(y_k - f_ik, s_ik^2) - (1/(2 M^2)) sum_i sum_j A(f_ik - f_jk, s_ik^2 + s_jk^2), with
+ *                  A(mu, s^2) = 2 s phi(mu/s) + mu (2 Phi(mu/s) - 1) and A(mu, 0) = |mu|   (QN_SCORE_CRPS)
+ *   row 4, 5       mean and variance (ddof = 1) over the members of f_mk                   (QN_SCORE_MOMENTS)
+ * Rows that `what` does not ask for are left untouched.  All arithmetic is float64 whatever the input type.  The log-sum-exp
+ * keeps a running maximum and both variances are Welford recurrences: a common offset of ll costs no digits and identical
+ * members give exactly 0.  The CRPS pair sum is O(M^2 K) (only j <= i is evaluated); with sigma = 0 and V = NULL it is the
+ * ensemble CRPS, with no transcendental.  Every sum runs in an order fixed by M alone, without atomics: an entry's six numbers
+ * do not depend on K, on the other entries of the call or on the launch geometry, and two calls give the same bits.
+ * A non-finite f, V or y, or sigma^2 + V_mk < 0, makes the requested rows of THAT entry NaN and changes no other entry; with
+ * V given, s_mk = 0 at an entry makes lppd and p_waic of that entry NaN (pit and crps take the degenerate forms above).
+ * QN_EINVAL with a message, before any pointer is touched: M < 2, K < 1, a bad dtype, what == 0 or unknown bits, sigma < 0
+ * or not finite, LPPD / PWAIC / PIT with sigma == 0 and V == NULL, a NULL F, Y or out (or workspace, if the CRPS is asked);
+ * a workspace that is too small is QN_EWORKSPACE.  qn_pred_score_workspace_bytes returns 0 for (M, K, what) the call would
+ * refuse (qn_last_error() says why) and needs no device; it is never 0 otherwise.  The workspace ([ceil(M / 32), K] float64
+ * partial pair sums) needs no initialisation and keeps no state. */
+#define QN_SCORE_LPPD 1
+#define QN_SCORE_PWAIC 2
+#define QN_SCORE_PIT 4
+#define QN_SCORE_CRPS 8
+#define QN_SCORE_MOMENTS 16
+#define QN_SCORE_NOUT 6
+size_t qn_pred_score_workspace_bytes(int64_t M, int64_t K, int what);
+int qn_pred_score(const void* F, const void* V, int dtype, const double* Y, int64_t M, int64_t K, double sigma, int what,
+                  double* out /* [QN_SCORE_NOUT, K] float64 */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic: y[i] = device tanh(x[i]) in float64 (the activation used by every kernel). */
 int qn_debug_tanh(const double* x, double* y, int64_t n, void* stream);
 /* Diagnostic: the variant the fused kernels use when all weights and inputs are finite and bounded

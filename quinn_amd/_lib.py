@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libquinn_amd.so")
-SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_adapt.hip", "qn_sgmcmc.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip"]
+SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_adapt.hip", "qn_sgmcmc.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip", "qn_score.hip"]
 # sources that #include another source (the second object of a file compiled in two parts): rebuilt when that one changes
 SOURCE_DEPS = {"qn_wide_u_i8.hip": ["qn_wide_i8.hip"], "qn_fused_d8.hip": ["qn_fused.hip"], "qn_fused_o16.hip": ["qn_fused.hip"]}
 
@@ -22,12 +22,13 @@ ARITH_PLAIN, ARITH_I8_FUSED, ARITH_I8_WIDE, ARITH_I8_LAYERS = 0, 1, 2, 3
 CURV_HESS_FULL, CURV_EF_DIAG, CURV_GGN_FULL, CURV_GGN_DIAG = 0, 1, 2, 3
 GLM_COV_FULL, GLM_COV_DIAG = 0, 1
 SWAG_INIT, SWAG_SGD, SWAG_SGD_COLLECT = 0, 1, 2
+SCORE_LPPD, SCORE_PWAIC, SCORE_PIT, SCORE_CRPS, SCORE_MOMENTS, SCORE_NOUT = 1, 2, 4, 8, 16, 6
 
 # every symbol include/quinn_amd.h declares (tests check the .so exports all of them)
 SYMBOLS = ["qn_mlp_desc_create", "qn_rnet_desc_create", "qn_rnet_desc_set_uses", "qn_mlp_desc_destroy", "qn_mlp_num_params", "qn_workspace_bytes",
            "qn_mlp_path", "qn_mlp_arith", "qn_mlp_desc_set_path", "qn_mlp_desc_set_plan_batch", "qn_mlp_sse_fwd", "qn_mlp_sse_parts", "qn_mlp_sse_fwd_parts", "qn_mlp_sse_fwdbwd", "qn_vi_sample_kl",
            "qn_vi_grad", "qn_adam_batched", "qn_mcmc_propose", "qn_mcmc_propose_hist", "qn_mcmc_hist_block_steps", "qn_mcmc_hist_block_coef_bytes", "qn_mcmc_propose_hist_block",
-           "qn_mcmc_apply_delta", "qn_mcmc_accept", "qn_mcmc_accept_propose", "qn_hmc_parts", "qn_hmc_begin", "qn_hmc_leap", "qn_hmc_accept", "qn_hmc_begin_s", "qn_hmc_leap_s", "qn_hmc_adapt", "qn_sg_rows", "qn_sg_step", "qn_pred_moments", "qn_curv_workspace_bytes", "qn_mlp_curv", "qn_glm_workspace_bytes", "qn_mlp_glm_predict", "qn_sobolev_workspace_bytes", "qn_mlp_input_jac", "qn_mlp_sobolev_fwdbwd", "qn_swag_step", "qn_swag_sample", "qn_kron_layout", "qn_kron_workspace_bytes", "qn_mlp_kron_factors", "qn_kron_glm_workspace_bytes", "qn_mlp_kron_glm_predict", "qn_kron_sample", "qn_chain_stats_workspace_bytes", "qn_chain_stats", "qn_debug_tanh", "qn_debug_tanh_finite", "qn_debug_tanh_table", "qn_last_error",
+           "qn_mcmc_apply_delta", "qn_mcmc_accept", "qn_mcmc_accept_propose", "qn_hmc_parts", "qn_hmc_begin", "qn_hmc_leap", "qn_hmc_accept", "qn_hmc_begin_s", "qn_hmc_leap_s", "qn_hmc_adapt", "qn_sg_rows", "qn_sg_step", "qn_pred_moments", "qn_curv_workspace_bytes", "qn_mlp_curv", "qn_glm_workspace_bytes", "qn_mlp_glm_predict", "qn_sobolev_workspace_bytes", "qn_mlp_input_jac", "qn_mlp_sobolev_fwdbwd", "qn_swag_step", "qn_swag_sample", "qn_kron_layout", "qn_kron_workspace_bytes", "qn_mlp_kron_factors", "qn_kron_glm_workspace_bytes", "qn_mlp_kron_glm_predict", "qn_kron_sample", "qn_chain_stats_workspace_bytes", "qn_chain_stats", "qn_pred_score_workspace_bytes", "qn_pred_score", "qn_debug_tanh", "qn_debug_tanh_finite", "qn_debug_tanh_table", "qn_last_error",
            "qn_version"]
 
 
@@ -214,6 +215,10 @@ def lib():
     L.qn_chain_stats_workspace_bytes.restype = sz
     L.qn_chain_stats.argtypes = [vp, i32, i32, i64, i64, i64, i32, i64, vp, vp, sz, vp]
     L.qn_chain_stats.restype = i32
+    L.qn_pred_score_workspace_bytes.argtypes = [i64, i64, i32]
+    L.qn_pred_score_workspace_bytes.restype = sz
+    L.qn_pred_score.argtypes = [vp, vp, i32, vp, i64, i64, f64, i32, vp, vp, sz, vp]
+    L.qn_pred_score.restype = i32
     L.qn_debug_tanh.argtypes = [vp, vp, i64, vp]
     L.qn_debug_tanh.restype = i32
     L.qn_debug_tanh_finite.argtypes = [vp, vp, i64, vp]

@@ -34,6 +34,7 @@ import warnings
 import numpy as np
 import torch
 
+from .. import _lib, scoring
 from ..ops import BatchedMLP, check_kron_args, kron_sample
 from .nn_rms import NN_RMS
 
@@ -310,19 +311,11 @@ class NN_Laplace(NN_RMS):
         return self.predict_ens(x, nens=nens)
 
     # -- linearised predictive -------------------------------------------------------------------
-    def predict_glm(self, x, msc=1, noise=False):
-        """Closed-form predictive of the network linearised at each member's MAP weights ("GLM" predictive):
-        member b predicts N(f_b(x_n), J_n Sigma_b J_n^T) and the members are mixed with equal weights (`glm_mixture`).
-        Returns (ymean (N,o), yvar (N,o) | None, ycov (N,o,o) | None); msc = 0 / 1 / 2 selects how much is returned.
-        `ycov` is the covariance ACROSS THE OUTPUTS at each query point -- not `predict_mom_sample`'s (N,N,o), which is the
-        covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal.
-        One `qn_mlp_glm_predict` call over all members ('kron': `qn_mlp_kron_glm_predict`, no p x p array); no weight draws and
-        no SVD.  Works for every la_type; with 'full' the covariance may not be positive semi-definite, and negative variances
-        are reported (warned about, not clipped)."""
-        if msc not in (0, 1, 2):
-            raise ValueError(f"msc={msc}, but needs to be 0, 1 or 2")
+    def _glm_members(self, x):
+        """The members' linearised predictives at x: (f [M, N, o] = f_b(x_n), S [M, N, o, o] = J_n Sigma_b J_n^T), float64
+        device tensors, from one `qn_mlp_glm_predict` call ('kron': `qn_mlp_kron_glm_predict`)."""
         if not self.means:
-            raise RuntimeError("predict_glm needs a fitted solver (fit or la_calc)")
+            raise RuntimeError("the linearised predictive needs a fitted solver (fit or la_calc)")
         x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
         op = BatchedMLP(self.arch, x, None, device=self._device)
         if self.la_type == 'kron':
@@ -338,9 +331,40 @@ class NN_Laplace(NN_RMS):
                     c = torch.as_tensor(np.ascontiguousarray(c), device=op.device)
                 sig.append(c)
             f, S = op.glm_predict(np.asarray(self.means), torch.stack(sig))
+        return f, S
+
+    def predict_glm(self, x, msc=1, noise=False):
+        """Closed-form predictive of the network linearised at each member's MAP weights ("GLM" predictive):
+        member b predicts N(f_b(x_n), J_n Sigma_b J_n^T) and the members are mixed with equal weights (`glm_mixture`).
+        Returns (ymean (N,o), yvar (N,o) | None, ycov (N,o,o) | None); msc = 0 / 1 / 2 selects how much is returned.
+        `ycov` is the covariance ACROSS THE OUTPUTS at each query point -- not `predict_mom_sample`'s (N,N,o), which is the
+        covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal.
+        One `qn_mlp_glm_predict` call over all members ('kron': `qn_mlp_kron_glm_predict`, no p x p array); no weight draws and
+        no SVD.  Works for every la_type; with 'full' the covariance may not be positive semi-definite, and negative variances
+        are reported (warned about, not clipped)."""
+        if msc not in (0, 1, 2):
+            raise ValueError(f"msc={msc}, but needs to be 0, 1 or 2")
+        if not self.means:
+            raise RuntimeError("predict_glm needs a fitted solver (fit or la_calc)")
+        f, S = self._glm_members(x)
         mean, cov = glm_mixture(f.cpu().numpy(), S.cpu().numpy(), self.datanoise ** 2 if noise else 0.0)
         var = np.stack([cov[:, k, k] for k in range(cov.shape[1])], axis=1)
         if np.any(var < 0):
             warnings.warn("predict_glm: negative predictive variance (the posterior covariance is not positive "
                           "semi-definite); values are not clipped.", RuntimeWarning)
         return mean, (var if msc >= 1 else None), (cov if msc == 2 else None)
+
+    def score_glm(self, x, y, noise=None, crps=True, levels=scoring.DEFAULT_LEVELS):
+        """Score the closed-form linearised predictive against the targets y `(N, o)` at x: the dict of `QUiNNBase.score`, with
+        member b predicting N(f_b(x_n)_k, noise^2 + (J_n Sigma_b J_n^T)_kk) per entry -- the members' means and the diagonal of
+        their predictive covariances go to `qn_pred_score` as F and V.  No weight draws; `noise` defaults to `datanoise`.
+        With la_type 'full' a negative predictive variance makes that entry's scores NaN."""
+        sigma = self._score_noise(noise)
+        y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
+        f, S = self._glm_members(x)
+        M = f.shape[0]
+        V = torch.diagonal(S, dim1=-2, dim2=-1).contiguous()
+        what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
+        yt = torch.as_tensor(y.reshape(-1), device=f.device)
+        rows = scoring.score_rows(f.contiguous().reshape(M, -1), yt, sigma, V.reshape(M, -1), what)
+        return scoring.summarise(rows.cpu().numpy(), y, levels)

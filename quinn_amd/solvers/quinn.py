@@ -13,7 +13,7 @@ import sys
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, scoring
 from ..ops import MLPArch, BatchedMLP, flatten_module
 
 
@@ -139,6 +139,46 @@ class QUiNNBase():
                                                   var.data_ptr() if var is not None else None,
                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qn_pred_moments")
         return mean.cpu().numpy(), (var.cpu().numpy() if var is not None else None)
+
+    # -- scores of the predictive against data (qn_pred_score) ---------------------------------------------
+    def _score_noise(self, noise):
+        """The data noise sigma of the Gaussian predictive: `noise`, or the one the last fit used where the solver keeps it."""
+        if noise is None:
+            lpinfo = getattr(self, 'lpinfo', None)
+            if lpinfo and 'sigma' in lpinfo.get('lparams', {}):
+                noise = lpinfo['lparams']['sigma']
+            else:
+                noise = getattr(self, 'datanoise', None)
+        if noise is None:
+            raise ValueError(f"{type(self).__name__} keeps no data noise: pass noise=")
+        return float(noise)
+
+    def score(self, x, y, noise=None, nsam=1000, crps=True, max_bytes=256 << 20, levels=scoring.DEFAULT_LEVELS, **ens_args):
+        """Score the solver's `nsam`-member predictive ensemble against the targets y `(N, o)` at x: the dict of
+        `scoring.summarise` (per entry lppd_k, p_waic_k, pit, crps_k, mean, var; scalars lppd, p_waic, elpd_waic, waic,
+        se_elpd, nlpd, crps, rmse, coverage, pit_hist).  Member m predicts N(f_m(x), noise^2); `noise` defaults to the data
+        noise of the last fit.  On the training data `waic` is the WAIC, on held-out data `nlpd` is the test negative log
+        predictive density.  The weights are drawn ONCE (`_ens_weights`; ens_args as in `predict_ens`, e.g. NN_MCMC's
+        `nburn`, `chain='all'`), then x is walked in row chunks whose `M x rows x o` predictions fit `max_bytes`: one batched
+        forward and one `qn_pred_score` per chunk, and only `6 x rows x o` doubles are downloaded.  An entry's scores do
+        not depend on the chunking.  crps=False skips the pair pass, which costs O(M^2) per entry."""
+        sigma = self._score_noise(noise)
+        x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
+        y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
+        W = self._ens_weights(nsam, **ens_args)
+        M, (N, o) = len(W), y.shape
+        esize = 4 if self._dtype == "float32" else 8
+        step = max(1, int(max_bytes) // (M * o * esize))
+        what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
+        rows = np.empty((_lib.SCORE_NOUT, N * o))
+        for lo in range(0, N, step):
+            hi = min(N, lo + step)
+            F = self._predict_batch_dev(W, x[lo:hi]).contiguous()
+            if F.dtype not in (torch.float32, torch.float64):
+                F = F.double()
+            yt = torch.as_tensor(y[lo:hi].reshape(-1), device=F.device)
+            rows[:, lo * o:hi * o] = scoring.score_rows(F.reshape(M, -1), yt, sigma, None, what).cpu().numpy()
+        return scoring.summarise(rows, y, levels)
 
     # -- figures (presentation only; same signatures and file names as quinn.py:106-260) ---------------
     @staticmethod
