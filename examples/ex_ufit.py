@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|sghmc|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -13,6 +13,8 @@ prints its closed-form linearised predictive (`predict_glm`) beside the sampled 
 `laplace_kron` is the same with the Kronecker-factored Gauss-Newton (`la_type='kron'`: two small factors per layer, no p x p matrix),
 `sghmc` is the device-only stochastic-gradient HMC (`engine='device'`; every chain draws its own minibatch on the GPU, cyclical
 step size, every 10th state stored; MLP network),
+`pt` is the device HMC with replica exchange (`engine='device'`, 8 ladders of 4 rungs; predictions and diagnostics from the cold
+chains; MLP network),
 and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
@@ -42,7 +44,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'sghmc', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -51,7 +53,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -71,6 +73,13 @@ def main(meth, quick=False, mlp=False):
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc',
                   sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True)
         predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+    elif meth == 'pt':
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                  sampler_params={'L': 3, 'epsilon': 0.0025, 'ladder': 4, 'beta_min': 0.05}, seeds=range(32), diagnostics=True)
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+        r = uqnet.mcmc_results
+        print("  swap acceptance per rung pair:", np.round(r['swap_rate'].reshape(-1, 4)[:, :-1].mean(axis=0), 3))
     elif meth == 'sghmc':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='sghmc', engine='device',
@@ -122,12 +131,12 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'sghmc'):
+    if meth in ('amcmc', 'hmc', 'pt', 'sghmc'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]
             print(f"  {label}: max R-hat {np.nanmax(d['rhat']):.3f}  min ESS {np.nanmin(d['ess']):.1f} of {d['n_draws']} draws"
-                  f" ({d['rhat'].size} entries, 8 chains)")
+                  f" ({d['rhat'].size} entries, 8 chains)")     # (pt: the 8 cold chains of 32)
     return ymean, ystd, rmse
 
 

@@ -323,6 +323,47 @@ int qn_hmc_adapt(const double* cur, const double* alphas, int nmcmc, const int64
                  int m, double target_accept, int collect, int finish, int freeze, int n, double* da, double* eps,
                  double* mean, double* m2, double* scale, void* stream);
 
+/* Replica exchange (parallel tempering) for the device HMC / MALA step (build-only; the reference has no such sampler;
+ * quinn_amd.mcmc.tempering restates the contract in numpy).  The C chains of a launch are whole ladders of R rungs,
+ * ladder-major: chain c is rung c % R of ladder c / R and samples pi^beta_c, beta [C] a DEVICE array with
+ * 1 = beta_0 > ... > beta_{R-1} > 0 inside a ladder.  Every stored log-posterior (cur_lp, best_lp, lps, the MAP) stays in the
+ * target's own, untempered units for every rung.
+ *
+ * qn_hmc_begin_t / qn_hmc_leap_t: qn_hmc_begin_s / qn_hmc_leap_s with the force beta_c * d logpost: gs_c = gs * beta_c
+ *   (gs = -0.5 / sigma^2) is formed first and stands wherever those calls use gs; drifts are unchanged.  Same grid, element ->
+ *   thread map, Philox keys and partial sums: with beta NULL (= 1) or all 1 the results are those calls' bit for bit.
+ * qn_hmc_accept_t: qn_hmc_accept with mh = exp((-beta_c clp + K_cur / 2) - (-beta_c plp + K_prop / 2)), clp / plp the
+ *   untempered log-posteriors; beta NULL or all 1: qn_hmc_accept bit for bit.
+ * qn_pt_swap: one exchange round, launched after the accept call (and the adapt call, if any) of a step.  With e = round & 1
+ *   the pairs are (c, c + 1) for c % R in {e, e + 2, ...}, c % R + 1 < R (deterministic even-odd scheme).  The step t just
+ *   decided is read from slot `parity` of step_ptr [2]; per pair, from slot `parity` of cur_lp [2, C]:
+ *     d = (beta_c - beta_{c+1}) * (lp_{c+1} - lp_c);   u = u01(words 0, 1) of Philox (seed, 2 t + 1, [chain0 + c : 24][6 : 4][0 : 36])
+ *   and the pair swaps iff both lp are finite and u < exp(d) (NaN: no swap).  On a swap the rows c and c + 1 of cur and
+ *   grad_cur [C, p] are exchanged in place, and chain[c, t, :], chain[c + 1, t, :] (chain [C, nmcmc + 1, p] or NULL) and
+ *   lps[c, t], lps[c + 1, t] (lps [C, nmcmc + 1]) are rewritten to the exchanged values: the stored row of step t is the state
+ *   step t + 1 starts from.  For EVERY chain, paired or not, slot 1 - parity receives cur_lp (exchanged or copied), best_lp
+ *   (copied: the MAP `best` stays with the chain slot).  rid [2, C] int32, the replica sitting in each chain slot, is double-
+ *   buffered by a parity of its OWN: slot rid_parity is read, slot 1 - rid_parity written (exchanged or copied), and the caller
+ *   flips rid_parity once per exchange round -- the accept calls in between flip the step parity but carry no rid over, so the
+ *   two parities differ whenever an odd number of steps lies between two rounds.  rep[c, round + 1] = that replica (rep [C, nrounds + 1] int32 or NULL; column 0 is the caller's).  swap_try[c] += 1
+ *   for the lower chain of a pair and swap_acc[c] += 1 on a swap (both [C] int64).  step_ptr[1 - parity] = t: no step was
+ *   taken, the caller only flips its parity (as after qn_sg_step(final)).  No atomics, no fences: two calls on equal inputs
+ *   give equal bits.  QN_EINVAL with a message, before any pointer is touched: R < 2, C % R != 0, chain0 % R != 0, C outside
+ *   1 .. 65535, p < 1, nmcmc < 1, round outside 0 .. nrounds - 1, a parity or rid_parity other than 0 / 1, a NULL pointer other than chain / rep. */
+int qn_hmc_begin_t(const double* cur, const double* grad_cur, double sigma, const double* eps, const double* scale,
+                   const double* beta, int C, int chain0, int64_t p, uint64_t seed, const int64_t* step_ptr, double* mom,
+                   double* q, double* kin_cur_parts, void* stream);
+int qn_hmc_leap_t(const void* grad_q, int dtype, double sigma, const double* eps, const double* scale, const double* beta,
+                  int last, int C, int64_t p, double* mom, double* q, double* kin_prop_parts, void* stream);
+int qn_hmc_accept_t(const double* q, const double* grad_q, const double* sse_q, const double* kin_cur_parts,
+                    const double* kin_prop_parts, double sigma, int n_rows, int C, int chain0, int64_t p, int nmcmc,
+                    uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best, double* best_lp, double* chain,
+                    double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr, int parity, const double* beta,
+                    void* stream);
+int qn_pt_swap(double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* chain, const double* beta,
+               int32_t* rid, int32_t* rep, int64_t* swap_acc, int64_t* swap_try, int64_t* step_ptr, int R, int round,
+               int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, int parity, int rid_parity, void* stream);
+
 /* Stochastic-gradient MCMC on the device (SGLD, SGHMC, optional cyclical step size; build-only, the reference has no such
  * sampler).  A step is qn_mlp_sse_fwdbwd on each chain's own n_batch rows followed by ONE qn_sg_step; nothing is read back.
  * Philox4x32-10 keyed by (seed, stream = inner step t, counter = [GLOBAL chain id = chain0 + c : 24][purpose : 4][index : 36]),

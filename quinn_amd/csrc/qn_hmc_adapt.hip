@@ -8,95 +8,9 @@
 // replaced by the per-element products (kick_c * s) and (eps_c * s).  Same grid, same element -> thread map, same Philox keys
 // and the same fixed-order partial sums, so with scale = 1 and equal eps_c the results are those kernels' bit for bit, and
 // qn_hmc_accept serves both.  HBM-bound elementwise work; all stores are ordinary vector stores, no atomics, no fences.
-#include "qn_mcmc_shared.h"
+#include "qn_hmc_step_s.h"      // k_hmc_begin_s / k_hmc_leap_s, shared with qn_temper.hip
 
 namespace {
-
-// mom = z + (hk_c s) g_cur;  q = cur + (eps_c s) mom;  K_cur partial = sum z^2       (hk_c = (eps_c / 2) gs, gs = -0.5 / sigma^2)
-// One Philox block = one PAIR of consecutive elements = one 16-byte access per array (8-byte aligned: rows of odd length).
-__global__ __launch_bounds__(HBLK) void k_hmc_begin_s(const double* __restrict__ cur, const double* __restrict__ gcur,
-                                                      const double* __restrict__ eps, const double* __restrict__ scale,
-                                                      double gs, int chain0, int64_t p, uint64_t seed,
-                                                      const int64_t* __restrict__ step_ptr, double* __restrict__ mom,
-                                                      double* __restrict__ q, double* __restrict__ kin_parts) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const uint64_t step = (uint64_t)*step_ptr;
-    const double eps_c = eps[b];
-    const double half_kick = 0.5 * eps_c * gs;
-    const int64_t base = (int64_t)b * p;
-    const int64_t npair = (p + 1) / 2;
-    const int64_t pchunk = (npair + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * pchunk, hi = lo + pchunk < npair ? lo + pchunk : npair;
-    double ss = 0.0;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += HBLK) {
-        Philox ph;
-        ph.gen(seed, 2 * step, ctr_of(chain0 + b, 0, (uint64_t)j));
-        double za, zb;
-        normal2(ph, za, zb);
-        const int64_t e = 2 * j;
-        const bool both = e + 1 < p;
-        const d2u one = {1.0, 1.0};
-        const d2u gv = ld2(gcur + base + e, both), cv = ld2(cur + base + e, both);
-        const d2u sv = scale ? ld2(scale + base + e, both) : one;
-        const double m0 = fma(half_kick * sv.x, gv.x, za);
-        const double q0 = fma(eps_c * sv.x, m0, cv.x);
-        ss = fma(za, za, ss);
-        double m1 = 0.0, q1 = 0.0;
-        if (both) {
-            m1 = fma(half_kick * sv.y, gv.y, zb);
-            q1 = fma(eps_c * sv.y, m1, cv.y);
-            ss = fma(zb, zb, ss);
-        }
-        st2(mom + base + e, m0, m1, both);
-        st2(q + base + e, q0, q1, both);
-    }
-    const double tot = block_sum_256(ss, red);
-    if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
-}
-
-// mom += (kick_c s) g;   last ? K_prop partial = sum mom^2 : q += (eps_c s) mom        (kick_c = f eps_c gs, f = 1 or 1/2)
-// The element -> thread map and the order of the sum of squares are k_hmc_leap's.  HS: a scale array is given (a compile-time
-// choice, so that the unrolled loads carry no per-element branch).
-template <typename TG, bool HS>
-__global__ __launch_bounds__(HBLK) void k_hmc_leap_s(const TG* __restrict__ g, const double* __restrict__ eps,
-                                                     const double* __restrict__ scale, double f, double gs, int last,
-                                                     int64_t p, double* __restrict__ mom, double* __restrict__ q,
-                                                     double* __restrict__ kin_parts) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const double eps_c = eps[b];
-    const double kick = f * eps_c * gs;
-    const int64_t base = (int64_t)b * p;
-    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
-    double ss = 0.0;
-    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
-        double gv[HUB], mv[HUB], qv[HUB], sv[HUB];
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            const bool in = e < hi;
-            gv[u] = in ? (double)g[base + e] : 0.0;
-            mv[u] = in ? mom[base + e] : 0.0;
-            qv[u] = (in && !last) ? q[base + e] : 0.0;
-            sv[u] = (HS && in) ? scale[base + e] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            if (e >= hi) break;
-            const double m = fma(kick * sv[u], gv[u], mv[u]);
-            mom[base + e] = m;
-            if (last) ss = fma(m, m, ss);
-            else q[base + e] = fma(eps_c * sv[u], m, qv[u]);
-        }
-    }
-    if (last) {
-        const double tot = block_sum_256(ss, red);
-        if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
-    }
-}
 
 // One warm-up step's adaptation.  Scalars (workgroup 0 of the chain, thread 0): the acceptance of the step just decided
 // is alphas[c, t] with t = step_ptr[par] (the slot the accept call wrote); a = min(1, mh), NaN -> 0;
@@ -178,10 +92,9 @@ extern "C" int qn_hmc_begin_s(const double* cur, const double* grad_cur, double 
         qn_set_error("qn_hmc_begin_s: bad argument");
         return QN_EINVAL;
     }
-    const double gs = -0.5 / (sigma * sigma);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_hmc_begin_s, dim3(hmc_parts(p), C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), cur, grad_cur,
-                       eps, scale, gs, chain0, p, seed, step_ptr, mom, q, kin_cur_parts);
+    hmc_begin_s_launch(cur, grad_cur, sigma, eps, scale, nullptr, C, chain0, p, seed, step_ptr, mom, q, kin_cur_parts,
+                       static_cast<hipStream_t>(stream));
     QN_HIP_CHECK(hipGetLastError());
     return QN_OK;
 }
@@ -193,24 +106,9 @@ extern "C" int qn_hmc_leap_s(const void* grad_q, int dtype, double sigma, const 
         qn_set_error("qn_hmc_leap_s: bad argument");
         return QN_EINVAL;
     }
-    const double gs = -0.5 / (sigma * sigma);
-    const double f = last ? 0.5 : 1.0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     (void)hipGetLastError();
-    const dim3 grid(hmc_parts(p), C), blk(HBLK);
-    const int l = last ? 1 : 0;
-    if (dtype == QN_F32 && scale)
-        hipLaunchKernelGGL((k_hmc_leap_s<float, true>), grid, blk, 0, st, (const float*)grad_q, eps, scale, f, gs, l, p, mom, q,
-                           kin_prop_parts);
-    else if (dtype == QN_F32)
-        hipLaunchKernelGGL((k_hmc_leap_s<float, false>), grid, blk, 0, st, (const float*)grad_q, eps, scale, f, gs, l, p, mom, q,
-                           kin_prop_parts);
-    else if (scale)
-        hipLaunchKernelGGL((k_hmc_leap_s<double, true>), grid, blk, 0, st, (const double*)grad_q, eps, scale, f, gs, l, p, mom,
-                           q, kin_prop_parts);
-    else
-        hipLaunchKernelGGL((k_hmc_leap_s<double, false>), grid, blk, 0, st, (const double*)grad_q, eps, scale, f, gs, l, p, mom,
-                           q, kin_prop_parts);
+    hmc_leap_s_launch(grad_q, dtype, sigma, eps, scale, nullptr, last, C, p, mom, q, kin_prop_parts,
+                      static_cast<hipStream_t>(stream));
     QN_HIP_CHECK(hipGetLastError());
     return QN_OK;
 }

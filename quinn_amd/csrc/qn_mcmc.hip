@@ -319,6 +319,9 @@ struct AcceptArgs {
     const double* kin_prop;               // [C, nkin]
     const double* gprop;                  // [C, p]
     double* gcur;                         // [C, p]
+    // tempered HMC (qn_hmc_accept_t): chain c targets pi^beta_c, so beta_c scales the potential in the MH ratio alone; every
+    // stored log-posterior stays untempered.  NULL: 1.
+    const double* beta;                   // [C]
 };
 
 // Optional fusion of the NEXT step's proposal into the accept kernel (it already has the new state in registers):
@@ -390,6 +393,7 @@ __global__ __launch_bounds__(ABLK) void k_accept(AcceptArgs a, const double* __r
     const double kp_l = lane < a.nkin ? a.kin_prop[(int64_t)b * a.nkin + lane] : 0.0;
     const double clp = cur_lp[so];
     const double blp = best_lp[so];
+    const double bc = a.beta ? a.beta[b] : 1.0;
     const int kc = hist ? kcur[so] : 0;
     // ---- the decision (every wave of every workgroup of the chain computes the same numbers in the same order)
     double sse = 0.0;
@@ -399,7 +403,8 @@ __global__ __launch_bounds__(ABLK) void k_accept(AcceptArgs a, const double* __r
     for (int i = 0; i < a.nkin; ++i) { kin_c += __shfl(kc_l, i, 64); kin_p += __shfl(kp_l, i, 64); }      // (nkin <= 64)
     const double plp = -(a.half_inv_sig2 * sse + a.lp_const);
     // exp(current_H - proposed_H), H = U + K, U = -log-posterior (mcmc.py:69-72); with K = 0 this is exp(plp - clp) exactly
-    const double mh = exp((-clp + 0.5 * kin_c) - (-plp + 0.5 * kin_p));
+    // (tempered: U = -beta_c log-posterior; bc = 1 leaves both products exact)
+    const double mh = exp((-(bc * clp) + 0.5 * kin_c) - (-(bc * plp) + 0.5 * kin_p));
     Philox ph;
     ph.gen(a.seed, 2 * (uint64_t)step + 1, ctr_of(a.chain0 + b, 2, 0));
     const double u = u01(ph.c[0], ph.c[1]);
@@ -665,7 +670,7 @@ static int accept_launch(const char* who, bool bad, AcceptArgs a, const NextArgs
 static AcceptArgs accept_args_mcmc(int kcap, int64_t pstride, int nparts, const double* hscale) {      // plain Metropolis
     AcceptArgs a;
     a.kcap = kcap; a.pstride = pstride; a.nparts = nparts; a.hscale = hscale;
-    a.nkin = 0; a.kin_cur = a.kin_prop = a.gprop = nullptr; a.gcur = nullptr;
+    a.nkin = 0; a.kin_cur = a.kin_prop = a.gprop = nullptr; a.gcur = nullptr; a.beta = nullptr;
     return a;
 }
 static const NextArgs NEXT_NONE = {0, 0, 0.0, 0.0, nullptr, nullptr, nullptr};
@@ -737,15 +742,35 @@ extern "C" int qn_hmc_leap(const void* grad_q, int dtype, double sigma, double e
     return QN_OK;
 }
 
+static int hmc_accept_any(const char* who, const double* beta, const double* q, const double* grad_q, const double* sse_q,
+                          const double* kin_cur_parts, const double* kin_prop_parts, double sigma, int n_rows, int C, int chain0,
+                          int64_t p, int nmcmc, uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best,
+                          double* best_lp, double* chain, double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr,
+                          int parity, void* stream) {
+    const bool bad = !grad_q || !kin_cur_parts || !kin_prop_parts || !grad_cur || !(sigma > 0.0);
+    AcceptArgs a;
+    a.kcap = 0; a.pstride = p; a.nparts = 1; a.hscale = nullptr;
+    a.nkin = hmc_parts(p); a.kin_cur = kin_cur_parts; a.kin_prop = kin_prop_parts; a.gprop = grad_q; a.gcur = grad_cur; a.beta = beta;
+    return accept_launch(who, bad, a, NEXT_NONE, q, sse_q, sigma, n_rows, C, chain0, p, nmcmc, seed, cur, cur_lp, best,
+                         best_lp, chain, lps, alphas, nacc, nullptr, nullptr, nullptr, nullptr, nullptr, step_ptr, parity, stream);
+}
+
 extern "C" int qn_hmc_accept(const double* q, const double* grad_q, const double* sse_q, const double* kin_cur_parts,
                              const double* kin_prop_parts, double sigma, int n_rows, int C, int chain0, int64_t p, int nmcmc,
                              uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best, double* best_lp,
                              double* chain, double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr, int parity,
                              void* stream) {
-    const bool bad = !grad_q || !kin_cur_parts || !kin_prop_parts || !grad_cur || !(sigma > 0.0);
-    AcceptArgs a;
-    a.kcap = 0; a.pstride = p; a.nparts = 1; a.hscale = nullptr;
-    a.nkin = hmc_parts(p); a.kin_cur = kin_cur_parts; a.kin_prop = kin_prop_parts; a.gprop = grad_q; a.gcur = grad_cur;
-    return accept_launch("qn_hmc_accept", bad, a, NEXT_NONE, q, sse_q, sigma, n_rows, C, chain0, p, nmcmc, seed, cur, cur_lp, best,
-                         best_lp, chain, lps, alphas, nacc, nullptr, nullptr, nullptr, nullptr, nullptr, step_ptr, parity, stream);
+    return hmc_accept_any("qn_hmc_accept", nullptr, q, grad_q, sse_q, kin_cur_parts, kin_prop_parts, sigma, n_rows, C, chain0, p,
+                          nmcmc, seed, cur, grad_cur, cur_lp, best, best_lp, chain, lps, alphas, nacc, step_ptr, parity, stream);
+}
+
+// qn_hmc_accept for chains that target pi^beta_c (replica exchange, qn_temper.hip): the same kernel, beta [C] in the MH ratio.
+// It lives here because k_accept does.
+extern "C" int qn_hmc_accept_t(const double* q, const double* grad_q, const double* sse_q, const double* kin_cur_parts,
+                               const double* kin_prop_parts, double sigma, int n_rows, int C, int chain0, int64_t p, int nmcmc,
+                               uint64_t seed, double* cur, double* grad_cur, double* cur_lp, double* best, double* best_lp,
+                               double* chain, double* lps, double* alphas, int64_t* nacc, int64_t* step_ptr, int parity,
+                               const double* beta, void* stream) {
+    return hmc_accept_any("qn_hmc_accept_t", beta, q, grad_q, sse_q, kin_cur_parts, kin_prop_parts, sigma, n_rows, C, chain0, p,
+                          nmcmc, seed, cur, grad_cur, cur_lp, best, best_lp, chain, lps, alphas, nacc, step_ptr, parity, stream);
 }

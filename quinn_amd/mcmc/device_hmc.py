@@ -23,12 +23,22 @@ sizes [C] and the scales [C, p] from device arrays; a warm-up step is followed b
 (window ends, counts) is static and host-known, so still nothing is read back.  Warm-up rows are stored like any other row
 (discard them with `nburn`); the results gain 'epsilon' [C], 'mass_scale' [C, p] (None without mass windows) and 'nwarm'.
 adapt = 0 (default) runs the fixed-step kernels exactly as before.
+
+`ladder` (an int R or a sequence of inverse temperatures) turns the chains into C / R replica-exchange ladders
+(`quinn_amd.mcmc.tempering` states the contract): chain c is rung c % R and samples pi^beta_r through qn_hmc_begin_t /
+qn_hmc_leap_t / qn_hmc_accept_t, from the per-chain step size epsilon / sqrt(beta_r) (the exact scaling for a Gaussian target;
+`adapt` then tunes each rung's step and mass as before), and every `swap_every`-th step, warm-up included, is followed by one
+qn_pt_swap launch (order within a step: accept, adapt, swap).  The results gain 'beta' [C], 'swap_rate' [C] (accepted / tried
+exchanges with the next rung; NaN for the top rung) and 'replica' [C, nrounds + 1] (the replica in each chain slot after every
+round; column 0 is the global chain id).  Use the cold chains (beta == 1) for inference.  A ladder cannot be captured in a graph.
+ladder = None (default) runs exactly what ran before, through the same entry points.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from .adapt import TARGET_ACCEPT, check_adapt_args, warmup_plan
+from .tempering import check_temper_args, check_whole_ladders
 from .device_engine import DeviceEngine
 
 
@@ -36,7 +46,7 @@ class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
     def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
-                 target_accept=None, adapt_mass=True):
+                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1):
         # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
         # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
         # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
@@ -49,6 +59,10 @@ class DeviceHMC(DeviceEngine):
         self.target_accept = TARGET_ACCEPT[self._kind] if target_accept is None else float(target_accept)
         self.adapt = check_adapt_args(adapt, self.target_accept)
         self.adapt_mass = bool(adapt_mass)
+        # replica exchange: the inverse temperatures of one ladder (None: no tempering) and the steps between exchange rounds
+        self.beta_min, self.swap_every = float(beta_min), swap_every
+        self._ladder = None if ladder is None else check_temper_args(ladder, beta_min, swap_every, chain0=self.chain0,
+                                                                     use_graph=self.use_graph)
 
     def _step(self, s, nmcmc):
         """Enqueue one HMC step on the current stream (reads slot s['par'] of the scalars, writes the other).  s['kern']: the
@@ -57,6 +71,7 @@ class DeviceHMC(DeviceEngine):
         st = self._stream()
         C, p = s['cur'].shape
         begin, begin_name, leap, leap_name, eps = s['kern']
+        accept, accept_name, accept_extra = s.get('accept') or (self._L.qn_hmc_accept, "qn_hmc_accept", ())
         _lib.check(begin(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, *eps, C, self.chain0, p, self.seed,
                          self._step_ptr(s), s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st), begin_name)
         for j in range(self.L):
@@ -66,13 +81,27 @@ class DeviceHMC(DeviceEngine):
             _lib.check(leap(s['gq'].data_ptr(), self.op.qdt, self.sigma, *eps, int(last), C, p, s['mom'].data_ptr(),
                             s['q'].data_ptr(), s['kprop'].data_ptr(), st), leap_name)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
-        _lib.check(self._L.qn_hmc_accept(
+        _lib.check(accept(
             s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
             self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
             s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
             s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
-            s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], st), "qn_hmc_accept")
+            s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], *accept_extra, st), accept_name)
         s['par'] ^= 1
+
+    def _swap_step(self, s, nmcmc):
+        """Enqueue exchange round s['round'] after the step just decided (and its adaptation); like `_adapt_step` it reads that
+        step from slot s['par'] of the step counter, and it writes the other slot of every scalar: the parity flips.  The
+        replica ids have a parity of their own (only exchange rounds write them): that of the round."""
+        C, p = s['cur'].shape
+        _lib.check(self._L.qn_pt_swap(
+            s['cur'].data_ptr(), s['gcur'].data_ptr(), s['cur_lp'].data_ptr(), s['best_lp'].data_ptr(), s['lps'].data_ptr(),
+            s['chain'].data_ptr() if s['chain'] is not None else None, s['beta'].data_ptr(), s['rid'].data_ptr(),
+            s['rep'].data_ptr(), s['swap_acc'].data_ptr(), s['swap_try'].data_ptr(), s['step'].data_ptr(), self._ladder.size,
+            s['round'], s['rep'].shape[1] - 1, C, self.chain0, p, nmcmc, self.seed, s['par'], s['round'] & 1, self._stream()),
+            "qn_pt_swap")
+        s['par'] ^= 1
+        s['round'] += 1
 
     def _adapt_step(self, s, nmcmc, a):
         """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
@@ -91,13 +120,23 @@ class DeviceHMC(DeviceEngine):
 
     def _clone(self, op, chain0):
         return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
-                         target_accept=self.target_accept, adapt_mass=self.adapt_mass)
+                         target_accept=self.target_accept, adapt_mass=self.adapt_mass, ladder=self._ladder,
+                         beta_min=self.beta_min, swap_every=self.swap_every)
+
+    def _check_groups(self, nmcmc, C, p):
+        if self._ladder is not None:
+            G = self._ngroups(C)
+            for g in range(G + 1):
+                check_whole_ladders(self._ladder.size, None, C * g // G)
 
     def _merge_groups(self, out, res, engs):
         if self.adapt:
             out['epsilon'] = torch.cat([r['epsilon'] for r in res])
             out['mass_scale'] = None if res[0]['mass_scale'] is None else torch.cat([r['mass_scale'] for r in res])
             out['nwarm'] = self.adapt
+        if self._ladder is not None:
+            for k in ('beta', 'swap_rate', 'replica'):
+                out[k] = torch.cat([r[k] for r in res])
 
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
@@ -105,6 +144,8 @@ class DeviceHMC(DeviceEngine):
         dev, f64 = self.dev, torch.float64
         cur = torch.as_tensor(param_ini, dtype=f64, device=dev).clone().reshape(-1, self.op.p)
         C, p = cur.shape
+        if self._ladder is not None:
+            check_whole_ladders(self._ladder.size, C, self.chain0)
         nk = int(self._L.qn_hmc_parts(p))
         f32op = self.op.tdt != f64
         sse0, g0 = self.op.sse_grad(cur if not f32op else cur.to(self.op.tdt))
@@ -118,22 +159,57 @@ class DeviceHMC(DeviceEngine):
                   'kern': (self._L.qn_hmc_begin, "qn_hmc_begin", self._L.qn_hmc_leap, "qn_hmc_leap", (self.epsilon,))})
         i = 0
         step = self._step
+        eps0 = self.epsilon
+        if self._ladder is not None:
+            # per-chain inverse temperature and step size epsilon / sqrt(beta_r); the replica trace starts at the global chain ids
+            R, nrounds = self._ladder.size, nmcmc // int(self.swap_every)
+            s['beta'] = torch.as_tensor(np.tile(self._ladder, C // R), dtype=f64, device=dev)
+            ids = torch.arange(self.chain0, self.chain0 + C, dtype=torch.int32, device=dev)
+            s['rid'] = torch.stack([ids, ids])
+            s['rep'] = torch.zeros(C, nrounds + 1, dtype=torch.int32, device=dev)
+            s['rep'][:, 0] = ids
+            s['swap_acc'] = torch.zeros(C, dtype=torch.int64, device=dev)
+            s['swap_try'] = torch.zeros(C, dtype=torch.int64, device=dev)
+            s['round'] = 0
+            eps0 = self.epsilon / torch.sqrt(s['beta'])
+            s['eps'] = eps0.clone()
+            s['kern'] = (self._L.qn_hmc_begin_t, "qn_hmc_begin_t", self._L.qn_hmc_leap_t, "qn_hmc_leap_t",
+                         (s['eps'].data_ptr(), None, s['beta'].data_ptr()))
+            s['accept'] = (self._L.qn_hmc_accept_t, "qn_hmc_accept_t", (s['beta'].data_ptr(),))
+            plain = self._step
+
+            def step(s, nmcmc, a=None):
+                """accept, adapt, swap: the launch order of a tempered step."""
+                plain(s, nmcmc)
+                if a is not None:
+                    self._adapt_step(s, nmcmc, a)
+                s['nstep'] = s.get('nstep', 0) + 1
+                if s['nstep'] % int(self.swap_every) == 0:
+                    self._swap_step(s, nmcmc)
         if self.adapt:
             # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
             plan = warmup_plan(self.adapt, self.adapt_mass)
             mass = any(a['finish'] for a in plan)
-            s['eps'] = torch.full((C,), self.epsilon, dtype=f64, device=dev)
+            if self._ladder is None:
+                s['eps'] = torch.full((C,), self.epsilon, dtype=f64, device=dev)
             s['da'] = torch.zeros(C, 4, dtype=f64, device=dev)          # (mu, Hbar, logbar, logeps)
-            s['da'][:, 0] = np.log(10 * self.epsilon)
-            s['da'][:, 3] = np.log(self.epsilon)
+            s['da'][:, 0] = np.log(10 * self.epsilon) if self._ladder is None else torch.log(10 * eps0)
+            s['da'][:, 3] = np.log(self.epsilon) if self._ladder is None else torch.log(eps0)
             s['scale'] = torch.ones(C, p, dtype=f64, device=dev) if mass else None
             s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
-            s['kern'] = (self._L.qn_hmc_begin_s, "qn_hmc_begin_s", self._L.qn_hmc_leap_s, "qn_hmc_leap_s",
-                         (s['eps'].data_ptr(), None if s['scale'] is None else s['scale'].data_ptr()))
+            scale_ptr = None if s['scale'] is None else s['scale'].data_ptr()
+            if self._ladder is None:
+                s['kern'] = (self._L.qn_hmc_begin_s, "qn_hmc_begin_s", self._L.qn_hmc_leap_s, "qn_hmc_leap_s",
+                             (s['eps'].data_ptr(), scale_ptr))
+            else:
+                s['kern'] = s['kern'][:4] + ((s['eps'].data_ptr(), scale_ptr, s['beta'].data_ptr()),)
             for a in plan:
-                step(s, nmcmc)
-                self._adapt_step(s, nmcmc, a)
+                if self._ladder is None:
+                    step(s, nmcmc)
+                    self._adapt_step(s, nmcmc, a)
+                else:
+                    step(s, nmcmc, a)
                 i += 1
                 yield
         if self.use_graph and nmcmc - i >= 4:
@@ -167,4 +243,6 @@ class DeviceHMC(DeviceEngine):
         out = self._results(s, nmcmc)
         if self.adapt:
             out.update(epsilon=s['eps'], mass_scale=s['scale'], nwarm=self.adapt)
+        if self._ladder is not None:
+            out.update(beta=s['beta'], swap_rate=s['swap_acc'].double() / s['swap_try'].double(), replica=s['rep'])
         return out

@@ -135,7 +135,8 @@ def gather_results(res, n_total, gather="all", gather_chain=None, max_bytes=DEFA
     tensors or numpy, this rank's shard) -> dict of numpy arrays.  The small entries follow `gather`; `chain`
     ([C, nmcmc+1, p], the large one: 43.6 GB per rank at cfg2) follows `gather_chain` (None: the same as `gather`).
     Adapted HMC / MALA runs add the per-chain `epsilon` [C] and `mass_scale` [C, p] (gathered like the small entries) and
-    the scalar `nwarm`, which is the same on every rank and passed through."""
+    the scalar `nwarm`, which is the same on every rank and passed through.  Replica-exchange runs add `beta` [C],
+    `swap_rate` [C] and `replica` [C, nrounds + 1], gathered like the small entries (shards are whole ladders)."""
     gc = gather if gather_chain is None else gather_chain
     return {k: (v if v is None or np.isscalar(v) else
                 gather_rows(v, n_total, dst=gc if k == "chain" else gather, max_bytes=max_bytes))
@@ -174,13 +175,16 @@ def adapt_keys(adapt, adapt_mass):
     return adapt, bool(adapt) and any(a['finish'] for a in warmup_plan(adapt, adapt_mass))
 
 
-def empty_results(nmcmc, p, adapt=0, mass=False):
+def empty_results(nmcmc, p, adapt=0, mass=False, nrounds=None):
     """Result dict of a rank that owns no chain (fewer chains than ranks).  adapt > 0: with the keys of an adapted HMC /
-    MALA run (mass: the run has mass windows, so `mass_scale` is an array on the ranks that own chains)."""
+    MALA run (mass: the run has mass windows, so `mass_scale` is an array on the ranks that own chains).  nrounds (not None):
+    with the keys of a replica-exchange run of that many exchange rounds."""
     out = {'chain': np.zeros((0, nmcmc + 1, p)), 'mapparams': np.zeros((0, p)), 'maxpost': np.zeros(0),
            'accrate': np.zeros(0), 'logpost': np.zeros((0, nmcmc + 1)), 'alphas': np.zeros((0, nmcmc + 1))}
     if adapt:
         out.update(epsilon=np.zeros(0), mass_scale=np.zeros((0, p)) if mass else None, nwarm=int(adapt))
+    if nrounds is not None:
+        out.update(beta=np.zeros(0), swap_rate=np.zeros(0), replica=np.zeros((0, int(nrounds) + 1), dtype=np.int32))
     return out
 
 

@@ -25,6 +25,7 @@ from ..mcmc.device_hmc import DeviceHMC
 from ..mcmc.device_mala import DeviceMALA
 from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
 from ..mcmc import diagnostics as diag
+from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
@@ -165,6 +166,12 @@ class NN_MCMC(QUiNNBase):
             so it works with gather_chain='none'; host engines: the numpy chain is uploaded in bounded pieces.  Multi-rank:
             each rank reduces its own chains, the small per-chain statistics follow `gather`.  diag_nburn: rows discarded
             first (None: nmcmc // 2).  False (default): nothing is computed and `self.diagnostics` is None.
+            sampler_params of 'hmc' / 'mala' with engine='device' may hold ladder=R (or a decreasing sequence of inverse
+            temperatures starting at 1), beta_min (default 0.01) and swap_every (default 1): replica exchange
+            (`quinn_amd.mcmc.tempering`).  The nchains chains are nchains / R ladders, chain c is rung c % R and samples
+            pi^beta_r; `mcmc_results` then also holds 'beta', 'swap_rate' and 'replica', and predict_ens / score with
+            chain='all', diagnostics=True and `diagnose` use the cold chains (beta == 1) only.  nchains (and every rank's
+            shard) must be a multiple of R; use_graph=True is refused.
             sampler='sgld' | 'sghmc' (engine='device' only; `quinn_amd.mcmc.device_sgmcmc`): stochastic-gradient Langevin /
             Hamiltonian dynamics, every chain on its own minibatch drawn on the device.  sampler_params: eta (step size),
             alpha ('sghmc' only: friction in (0, 1], default 0.1), batch (rows per chain and step, with replacement; None: all
@@ -233,14 +240,30 @@ class NN_MCMC(QUiNNBase):
             if sampler not in DEVICE_ENGINES:
                 raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld' and 'sghmc'")
             # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
+            nrounds = None
+            if sampler_params.get('ladder') is not None and sampler in ('hmc', 'mala'):
+                # replica exchange: all chains, and this rank's shard of them, are whole ladders (refused before any launch)
+                R = check_temper_args(sampler_params['ladder'], sampler_params.get('beta_min', 0.01),
+                                      sampler_params.get('swap_every', 1), C=ctot,
+                                      use_graph=sampler_params.get('use_graph', False)).size
+                check_whole_ladders(R, hi - lo, lo)
+                nrounds = nmcmc // int(sampler_params.get('swap_every', 1))
             eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, **sampler_params)
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
             else:
-                res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)))
+                res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)),
+                                    nrounds=nrounds)
             if diagnostics:
-                # from the engine's device tensors, before they are downloaded (or not: gather_chain='none')
-                self.diagnostics = self._fit_diagnostics(res['chain'], res['logpost'], diag_nburn, ctot, gather)
+                # from the engine's device tensors, before they are downloaded (or not: gather_chain='none'); of a
+                # replica-exchange run the cold chains only (rung 0 of every ladder: shards are whole ladders)
+                dch, dlp, dtot = res['chain'], res['logpost'], ctot
+                if nrounds is not None:
+                    if dch is None:
+                        raise ValueError("diagnostics=True needs the stored chain")
+                    cp = (lambda v: v.contiguous()) if isinstance(dch, torch.Tensor) else np.ascontiguousarray
+                    dch, dlp, dtot = cp(dch[::R]), cp(dlp[::R]), ctot // R        # (a copy of 1 / R of the chain)
+                self.diagnostics = self._fit_diagnostics(dch, dlp, diag_nburn, dtot, gather)
             # the single collective, at the end, straight from the device tensors (world == 1: a device->host copy)
             res = gather_results(res, ctot, gather, gather_chain)
             self.mcmc_results = res
@@ -295,6 +318,9 @@ class NN_MCMC(QUiNNBase):
         samples = np.asarray(self.samples)
         if samples.ndim == 2:
             samples = samples[None]
+        cold = self._cold_chains()
+        if cold is not None:
+            samples = samples[cold]
         out = {'params': diag.diagnose_chains(samples, nburn, device=self._device)}
         if x is not None:
             C, T, p = samples.shape
@@ -337,12 +363,23 @@ class NN_MCMC(QUiNNBase):
             cm = self.cmode[0 if chain is None else chain]
         return self.predict_sample(x, cm)
 
+    def _cold_chains(self):
+        """Indices of the cold chains (beta == 1) of a replica-exchange fit whose results this rank holds for every stored
+        chain; None for any other fit."""
+        beta = getattr(self, 'mcmc_results', {}).get('beta')
+        if beta is None or np.ndim(beta) != 1 or np.ndim(self.samples) != 3 or len(beta) != self.samples.shape[0]:
+            return None
+        return np.flatnonzero(np.asarray(beta) == 1.0)
+
     def _ens_weights(self, nens=10, nburn=1000, chain=0):
         nens = 10 if nens is None else nens
         if isinstance(chain, str):
             if chain != 'all':
                 raise ValueError("chain is an int or 'all'")
             samples = self.samples if self.samples.ndim == 3 else self.samples[None]
+            cold = self._cold_chains()
+            if cold is not None:
+                samples = samples[cold]
             picks = diag.pooled_rows(samples.shape[0], samples.shape[1], nens, nburn)
             return np.concatenate([samples[c][rows, :] for c, rows in picks])
         samples = self.samples if self.samples.ndim == 2 else self.samples[chain]
@@ -358,5 +395,6 @@ class NN_MCMC(QUiNNBase):
         nburn + j*int((len-nburn)/nens) of the chain (nn_mcmc.py:194-199) -- one batched
         forward instead of M sequential ones.  `chain` picks the chain of a multi-chain fit; chain='all' pools the
         chains: chain c contributes nens // C + (c < nens % C) draws, thinned by the same rule with that count, ordered
-        chain-major, still one batched forward."""
+        chain-major, still one batched forward.  After a replica-exchange fit chain='all' pools the cold chains (beta == 1)
+        only; an int indexes all chains as before."""
         return self._predict_ens_dev(x, nens, nburn, chain).double().cpu().numpy()
