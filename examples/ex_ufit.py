@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -15,6 +15,8 @@ prints its closed-form linearised predictive (`predict_glm`) beside the sampled 
 step size, every 10th state stored; MLP network),
 `pt` is the device HMC with replica exchange (`engine='device'`, 8 ladders of 4 rungs; predictions and diagnostics from the cold
 chains; MLP network),
+`prior` is the device HMC with the Gaussian weight prior `priorsigma=1.0` (`engine='device'`; MLP network), printed beside the same
+run without a prior and a `laplace_ggn` fit with the same `priorsigma` -- the Laplace approximation of the posterior it samples,
 and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
@@ -44,7 +46,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -53,7 +55,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -86,6 +88,25 @@ def main(meth, quick=False, mlp=False):
                   sampler_params={'eta': 4e-6, 'alpha': 0.1, 'batch': 8, 'thin': 10, 'schedule': 'cyclic', 'cycles': 4,
                                   'explore_frac': 0.25}, seeds=range(8), diagnostics=True)
         predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+    elif meth == 'prior':
+        others, ps = {}, 1.0
+        xg = scale01ToDom(np.linspace(0.0, 1.0, 11), domain)[:, np.newaxis]
+        for label, prior in (('no prior', None), ('priorsigma = %g' % ps, ps)):      # (the fit with the prior last: it is `uqnet`)
+            uqnet = NN_MCMC(nnet, verbose=not quick)
+            uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                      sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True, priorsigma=prior)
+            ye = uqnet.predict_ens(xg, nens=100 // k * 2, nburn=1000 // k, chain='all')
+            others['HMC, ' + label] = (ye.mean(axis=0)[:, 0], ye.std(axis=0, ddof=1)[:, 0])
+            w = uqnet.samples[:, 1000 // k:].reshape(-1, uqnet.pdim)
+            print(f"  HMC, {label}: mean |w|^2 / p over the kept rows {np.mean(w * w):.4f}, best log-posterior "
+                  f"{np.max(uqnet.mcmc_results['maxpost']):.2f}")
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+        la = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='ggn', datanoise=datanoise, priorsigma=ps)
+        la.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
+        yl = la.predict_ens(xg, nens=111)
+        others['laplace_ggn, priorsigma = %g' % ps] = (yl.mean(axis=0)[:, 0], yl.std(axis=0, ddof=1)[:, 0])
+        for label, (m, s) in others.items():
+            print(f"  {label}: predictive std on the grid " + " ".join(f"{v:.3f}" for v in s))
     elif meth == 'vi':
         uqnet = NN_VI(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, val=[xval, yval], datanoise=datanoise, lrate=0.01, batch_size=None, nsam=1,
@@ -131,7 +152,7 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'pt', 'sghmc'):
+    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]

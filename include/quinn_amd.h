@@ -397,6 +397,29 @@ int qn_sg_step(double* theta, double* v, const void* grad, int dtype, const doub
                int final, int C, int chain0, int64_t p, int nstore, uint64_t seed, void* theta_op, double* best, double* best_lp,
                double* chain, double* lps, int32_t* rows, int64_t* step_ptr, int parity, void* stream);
 
+/* Fold an isotropic Gaussian weight prior N(0, priorsigma^2 I) into the outputs of a forward / gradient call (build-only; the
+ * reference has no prior in NN_MCMC).  For every chain c < C, W [C, p] float64:
+ *     grad[c, j]            <- grad[c, j] + (2 lam) * W[c, j]           grad [C, p] of dtype gdtype (QN_F64 / QN_F32) or NULL
+ *     sse[c * sse_stride]   <- sse[c * sse_stride] + (lam * sum_j W[c, j]^2 + c0)      sse float64, or NULL
+ * lam > 0 and c0 finite are host scalars.  With lam = sigma^2 / priorsigma^2 and c0 = sigma^2 p log(2 pi priorsigma^2) the
+ * sampler kernels, which form log-posteriors and forces as gs * sse and gs * grad with gs = -0.5 / sigma^2, then see
+ *     gs sse' = gs sse + log N(w; 0, priorsigma^2 I)   (normaliser included),       gs grad' = gs grad - w / priorsigma^2:
+ * one launch behind every qn_mlp_sse_fwd / qn_mlp_sse_fwd_parts / qn_mlp_sse_fwdbwd call gives the accept, leapfrog, adapt,
+ * swap and SG kernels the posterior with the prior (sse_stride = the number of parts after qn_mlp_sse_fwd_parts: column 0
+ * receives the term, the accept kernel's left-to-right sum is unchanged).  A minibatch call multiplies lam and c0 by
+ * n_batch / n_rows, which qn_sg_step's (n_rows / n_batch) undoes: the prior is exact, only the likelihood is estimated.
+ * Arithmetic: every gradient entry is formed in float64 with one rounding per operation -- the product (2 lam) * w, then the
+ *   sum, no contraction; a QN_F32 gradient is widened, updated in float64 and rounded once.  The sum of squares is added in a
+ *   fixed order that depends on p alone -- not on C, the chain's place in the launch or the grid (workgroup 0 of every chain
+ *   sums the whole row and is the only writer of the chain's sse entry; the other columns of a strided sse are not touched).
+ *   No atomics, no fences: two calls on equal inputs give equal bits, and a chain's result is the same launched alone or among
+ *   others.  Rows need 8-byte alignment only.  Non-finite weights propagate: an Inf or NaN in W[c] makes sse[c] +Inf or NaN and
+ *   touches no other chain.
+ * QN_EINVAL with a message, before any pointer is touched: W NULL; grad and sse both NULL; lam not > 0 or not finite; c0 not
+ *   finite; C outside 1 .. 65535; p < 1; sse_stride < 1 with sse given; a gdtype other than the two with grad given. */
+int qn_prior_fold(const double* W, double lam, double c0, void* grad, int gdtype, double* sse, int sse_stride, int C, int64_t p,
+                  void* stream);
+
 /* Moments of a predictive ensemble on the device (QUiNNBase.predict_mom_sample, quinn/solvers/quinn.py:75-104):
  * Y [M, K] dtype = M members x K = N * o prediction entries as qn_mlp_sse_fwd writes them ([B, Nb, o] with B = M);
  * mean_out [K], var_out [K] (unbiased, ddof = 1; NULL to skip; needs M >= 2), float64.  The per-output covariance of

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libquinn_amd.so")
-SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_adapt.hip", "qn_temper.hip", "qn_sgmcmc.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip", "qn_score.hip"]
+SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_adapt.hip", "qn_temper.hip", "qn_sgmcmc.hip", "qn_prior.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip", "qn_score.hip"]
 # sources that #include another source (the second object of a file compiled in two parts): rebuilt when that one changes
 SOURCE_DEPS = {"qn_wide_u_i8.hip": ["qn_wide_i8.hip"], "qn_fused_d8.hip": ["qn_fused.hip"], "qn_fused_o16.hip": ["qn_fused.hip"]}
 
@@ -28,7 +28,7 @@ SCORE_LPPD, SCORE_PWAIC, SCORE_PIT, SCORE_CRPS, SCORE_MOMENTS, SCORE_NOUT = 1, 2
 SYMBOLS = ["qn_mlp_desc_create", "qn_rnet_desc_create", "qn_rnet_desc_set_uses", "qn_mlp_desc_destroy", "qn_mlp_num_params", "qn_workspace_bytes",
            "qn_mlp_path", "qn_mlp_arith", "qn_mlp_desc_set_path", "qn_mlp_desc_set_plan_batch", "qn_mlp_sse_fwd", "qn_mlp_sse_parts", "qn_mlp_sse_fwd_parts", "qn_mlp_sse_fwdbwd", "qn_vi_sample_kl",
            "qn_vi_grad", "qn_adam_batched", "qn_mcmc_propose", "qn_mcmc_propose_hist", "qn_mcmc_hist_block_steps", "qn_mcmc_hist_block_coef_bytes", "qn_mcmc_propose_hist_block",
-           "qn_mcmc_apply_delta", "qn_mcmc_accept", "qn_mcmc_accept_propose", "qn_hmc_parts", "qn_hmc_begin", "qn_hmc_leap", "qn_hmc_accept", "qn_hmc_begin_s", "qn_hmc_leap_s", "qn_hmc_adapt", "qn_hmc_begin_t", "qn_hmc_leap_t", "qn_hmc_accept_t", "qn_pt_swap", "qn_sg_rows", "qn_sg_step", "qn_pred_moments", "qn_curv_workspace_bytes", "qn_mlp_curv", "qn_glm_workspace_bytes", "qn_mlp_glm_predict", "qn_sobolev_workspace_bytes", "qn_mlp_input_jac", "qn_mlp_sobolev_fwdbwd", "qn_swag_step", "qn_swag_sample", "qn_kron_layout", "qn_kron_workspace_bytes", "qn_mlp_kron_factors", "qn_kron_glm_workspace_bytes", "qn_mlp_kron_glm_predict", "qn_kron_sample", "qn_chain_stats_workspace_bytes", "qn_chain_stats", "qn_pred_score_workspace_bytes", "qn_pred_score", "qn_debug_tanh", "qn_debug_tanh_finite", "qn_debug_tanh_table", "qn_last_error",
+           "qn_mcmc_apply_delta", "qn_mcmc_accept", "qn_mcmc_accept_propose", "qn_hmc_parts", "qn_hmc_begin", "qn_hmc_leap", "qn_hmc_accept", "qn_hmc_begin_s", "qn_hmc_leap_s", "qn_hmc_adapt", "qn_hmc_begin_t", "qn_hmc_leap_t", "qn_hmc_accept_t", "qn_pt_swap", "qn_sg_rows", "qn_sg_step", "qn_prior_fold", "qn_pred_moments", "qn_curv_workspace_bytes", "qn_mlp_curv", "qn_glm_workspace_bytes", "qn_mlp_glm_predict", "qn_sobolev_workspace_bytes", "qn_mlp_input_jac", "qn_mlp_sobolev_fwdbwd", "qn_swag_step", "qn_swag_sample", "qn_kron_layout", "qn_kron_workspace_bytes", "qn_mlp_kron_factors", "qn_kron_glm_workspace_bytes", "qn_mlp_kron_glm_predict", "qn_kron_sample", "qn_chain_stats_workspace_bytes", "qn_chain_stats", "qn_pred_score_workspace_bytes", "qn_pred_score", "qn_debug_tanh", "qn_debug_tanh_finite", "qn_debug_tanh_table", "qn_last_error",
            "qn_version"]
 
 
@@ -187,6 +187,8 @@ def lib():
     L.qn_sg_step.argtypes = [vp, vp, vp, i32, vp, f64, i32, i32, f64, f64, f64, i32, i64, f64, i32, i32, i32, i32, i64, i32, u64,
                              vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.qn_sg_step.restype = i32
+    L.qn_prior_fold.argtypes = [vp, f64, f64, vp, i32, vp, i32, i32, i64, vp]
+    L.qn_prior_fold.restype = i32
     L.qn_pred_moments.argtypes = [vp, i32, i64, i64, vp, vp, vp]
     L.qn_pred_moments.restype = i32
     L.qn_curv_workspace_bytes.argtypes = [vp, i32, i32, i32]

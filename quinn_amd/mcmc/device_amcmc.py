@@ -33,6 +33,10 @@ proposal's ingredients and the chain history in HBM and never synchronises with 
 Same target distribution and the same adaptation schedule as the reference; the random streams
 differ (Philox instead of numpy MT19937, sample-space draw instead of an SVD factor), so chains agree
 with the host sampler in distribution, not bit for bit.  Use `AMCMC` for bit-exact parity.
+
+`priorsigma` = s adds the Gaussian weight prior N(0, s^2 I) (`quinn_amd.mcmc.prior`): one qn_prior_fold launch behind the initial
+forward and every proposal's forward adds lam |w|^2 + c0 to column 0 of the SSE parts, which the accept kernel sums as before.
+None (default): no such launch.
 """
 import os
 import sys
@@ -63,14 +67,14 @@ def _toc(dev, t0, what, *args):
 class DeviceAMCMC(DeviceEngine):
     def __init__(self, op, sigma, gamma=0.1, t0=100, tadapt=1000, cov_ini=None, seed=0,
                  use_graph=False, max_history_bytes=64 << 30, chain0=0, fuse_propose=True, groups=None, max_rows=4096,
-                 overlap_hist=True, hist_scale0=256.0, pause_gc=True):
+                 overlap_hist=True, hist_scale0=256.0, pause_gc=True, priorsigma=None):
         if op.dtype != "float64":
             raise NotImplementedError("the device AMCMC engine runs the float64 operator")
         # groups > 1: a group's accept / propose kernel (a chain of memory round trips that leaves the GPU idle: 8.7 of a step's
         # 84 us at cfg2) overlaps the other group's forward kernel.  None: 2 groups from 32 chains on (measured at cfg2: 11.9 ->
         # 12.4 k steps/s before the first adaptation; 4 groups are bound by the enqueuing thread) when the fused kernels run the
         # network, else 1
-        super().__init__(op, sigma, seed, chain0, use_graph, groups)
+        super().__init__(op, sigma, seed, chain0, use_graph, groups, priorsigma)
         self.gamma, self.t0, self.tadapt = gamma, int(t0), int(tadapt)
         self.cov_ini = cov_ini
         self.max_history_bytes = int(max_history_bytes)
@@ -141,6 +145,12 @@ class DeviceAMCMC(DeviceEngine):
                 int(t), s_iso, prop.data_ptr(), s['par'], nparts, self._stream()), "qn_mcmc_accept_propose")
         s['par'] ^= 1              # the kernel read slot `par` of the per-chain scalars / step counter and wrote the other
 
+    def _sse_parts_prior(self, prop):
+        """The proposal's SSE parts with the prior's term in column 0 (the accept kernel adds the parts left to right)."""
+        parts = self.op.sse_parts(prop)
+        self.op.prior_fold(prop, *self._prior, sse=parts, sse_stride=parts.shape[1])
+        return parts
+
     def _ngroups(self, C):
         if self.groups is None:
             return 2 if C >= 32 and self.cov_ini is None and self.op.path(C) == _lib.PATH_FUSED else 1
@@ -169,7 +179,8 @@ class DeviceAMCMC(DeviceEngine):
     def _clone(self, op, chain0):
         return DeviceAMCMC(op, self.sigma, self.gamma, self.t0, self.tadapt, self.cov_ini, self.seed, self.use_graph,
                            self.max_history_bytes, chain0, self.fuse_propose, max_rows=self.max_rows,
-                           overlap_hist=self.overlap_hist, hist_scale0=self.hist_scale0, pause_gc=False)
+                           overlap_hist=self.overlap_hist, hist_scale0=self.hist_scale0, pause_gc=False,
+                           priorsigma=self.priorsigma)
 
     def _merge_groups(self, out, res, engs):
         self.last_state, self.last_states = None, [e.last_state for e in engs]      # (diagnostics: per group)
@@ -394,7 +405,12 @@ class DeviceAMCMC(DeviceEngine):
         if C * kcap * pstride * 2 + extra > self.max_history_bytes:
             raise MemoryError(f"state history {C} x {kcap} x {pstride} float16 (+ {extra >> 20} MiB of compression work space) exceeds max_history_bytes="
                               f"{self.max_history_bytes}: lower max_rows or raise the limit")
-        s = self._new_state(cur, self.op.sse(cur), nmcmc, store_chain, chain_out)
+        sse0 = self.op.sse(cur)
+        sse_parts = self.op.sse_parts                                        # no prior: exactly the calls made without one
+        if self._prior is not None:
+            self.op.prior_fold(cur, *self._prior, sse=sse0)
+            sse_parts = self._sse_parts_prior
+        s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
         s.update({'x0': cur.clone(), 'hist': torch.empty(C, kcap, pstride, dtype=torch.float16, device=dev),
                   'hscale': torch.full((C,), self.hist_scale0, dtype=f64, device=dev),
                   'mult': torch.zeros(C, kcap, dtype=torch.int32, device=dev),
@@ -424,14 +440,14 @@ class DeviceAMCMC(DeviceEngine):
                 for _ in range(n):
                     self._propose(None, None, 0.0, s, z)
                     prop.copy_(s['cur'] + z @ state['L'].T)
-                    self._accept(s, prop, self.op.sse_parts(prop), nmcmc)
+                    self._accept(s, prop, sse_parts(prop), nmcmc)
                 return False
             have = state['have_prop']
             for k in range(n):
                 if not have:
                     self._propose(s['cur'], std0, 0.1, s, prop)
                 nxt = (1, std0, 0.1, None, 0, 0.0) if fuse and (k + 1 < n or last_fused) else None
-                self._accept(s, prop, self.op.sse_parts(prop), nmcmc, nxt)
+                self._accept(s, prop, sse_parts(prop), nmcmc, nxt)
                 have = nxt is not None
             return have
 
@@ -468,7 +484,7 @@ class DeviceAMCMC(DeviceEngine):
                 if not have:
                     self._apply_delta(s, snap, dl, t, prop)
                 nxt = (2, None, 0.0, dl, t + 1, snap['s_iso']) if fuse and t + 1 < nsteps else None
-                self._accept(s, prop, self.op.sse_parts(prop), nmcmc, nxt)
+                self._accept(s, prop, sse_parts(prop), nmcmc, nxt)
                 have = nxt is not None
 
         def capture(fn):

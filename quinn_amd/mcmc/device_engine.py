@@ -1,5 +1,5 @@
-"""What the device samplers (`DeviceAMCMC`, `DeviceHMC`, `DeviceMALA`) share: the engine's identity (operator, noise level,
-seed, global id of the first chain), the per-run state the accept kernel maintains, the result dict, and `run`, which drives a
+"""What the device samplers (`DeviceAMCMC`, `DeviceHMC`, `DeviceMALA`, `DeviceSGHMC`, `DeviceSGLD`) share: the engine's identity
+(operator, noise level, optional Gaussian weight prior, seed, global id of the first chain), the per-run state the accept kernel maintains, the result dict, and `run`, which drives a
 sampler's step generator (`_run_gen`) for all chains at once or for groups of chains side by side on their own HIP streams."""
 import ctypes
 
@@ -8,6 +8,7 @@ import torch
 
 from .. import _lib
 from ..ops import BatchedMLP
+from .prior import check_priorsigma, fold_constants
 
 
 def _drain(gen):
@@ -22,8 +23,12 @@ class DeviceEngine:
     """A sampler supplies `_run_gen(nmcmc, param_ini, store_chain, verbose, chain_out=None)` (a generator that yields after
     every enqueued block of steps and returns the result dict), `_ngroups(C)` and `_clone(op, chain0)`."""
 
-    def __init__(self, op: BatchedMLP, sigma, seed, chain0, use_graph, groups):
+    def __init__(self, op: BatchedMLP, sigma, seed, chain0, use_graph, groups, priorsigma=None):
         self.op, self.sigma = op, float(sigma)
+        # isotropic Gaussian weight prior N(0, priorsigma^2 I) (`quinn_amd.mcmc.prior`): one qn_prior_fold launch behind every
+        # forward / gradient call puts it into the SSE and d SSE / d W the sampler kernels read.  None: no prior, no launch
+        self.priorsigma = check_priorsigma(priorsigma)
+        self._prior = None if self.priorsigma is None else fold_constants(self.sigma, self.priorsigma, op.p)
         self.dev = op.device
         self.seed = int(seed) & (2 ** 63 - 1)
         self.chain0 = int(chain0)          # global id of this engine's first chain (random streams are keyed by it)

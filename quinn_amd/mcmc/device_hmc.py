@@ -32,6 +32,11 @@ qn_pt_swap launch (order within a step: accept, adapt, swap).  The results gain 
 exchanges with the next rung; NaN for the top rung) and 'replica' [C, nrounds + 1] (the replica in each chain slot after every
 round; column 0 is the global chain id).  Use the cold chains (beta == 1) for inference.  A ladder cannot be captured in a graph.
 ladder = None (default) runs exactly what ran before, through the same entry points.
+
+`priorsigma` = s puts the Gaussian weight prior N(0, s^2 I) on the target (`quinn_amd.mcmc.prior`): one qn_prior_fold launch behind
+the initial and every leapfrog gradient call adds lam |q|^2 + c0 to the SSE and 2 lam q to the gradient (q: the float64 positions),
+and everything above -- forces, accept test, warm-up, ladder, graph, groups -- runs on the posterior with the prior, untouched.
+priorsigma = None (default) makes no such launch.
 """
 import numpy as np
 import torch
@@ -46,14 +51,14 @@ class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
     def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
-                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1):
+                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None):
         # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
         # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
         # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
         self.epsilon, self.L = float(epsilon), int(L)
         if self.L < 1:
             raise ValueError("HMC needs L >= 1 leapfrog steps")
-        super().__init__(op, sigma, seed, chain0, use_graph, groups)
+        super().__init__(op, sigma, seed, chain0, use_graph, groups, priorsigma)
         # warm-up: `adapt` steps of dual averaging from `epsilon` towards `target_accept` (default 0.8; MALA 0.574) and, with
         # adapt_mass, Stan's mass windows; 0: the fixed-step kernels
         self.target_accept = TARGET_ACCEPT[self._kind] if target_accept is None else float(target_accept)
@@ -78,6 +83,8 @@ class DeviceHMC(DeviceEngine):
             last = j == self.L - 1
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
+            if self._prior is not None:                                       # (the float64 positions, also under a float32 operator)
+                self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
             _lib.check(leap(s['gq'].data_ptr(), self.op.qdt, self.sigma, *eps, int(last), C, p, s['mom'].data_ptr(),
                             s['q'].data_ptr(), s['kprop'].data_ptr(), st), leap_name)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
@@ -121,7 +128,7 @@ class DeviceHMC(DeviceEngine):
     def _clone(self, op, chain0):
         return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
                          target_accept=self.target_accept, adapt_mass=self.adapt_mass, ladder=self._ladder,
-                         beta_min=self.beta_min, swap_every=self.swap_every)
+                         beta_min=self.beta_min, swap_every=self.swap_every, priorsigma=self.priorsigma)
 
     def _check_groups(self, nmcmc, C, p):
         if self._ladder is not None:
@@ -149,6 +156,8 @@ class DeviceHMC(DeviceEngine):
         nk = int(self._L.qn_hmc_parts(p))
         f32op = self.op.tdt != f64
         sse0, g0 = self.op.sse_grad(cur if not f32op else cur.to(self.op.tdt))
+        if self._prior is not None:
+            self.op.prior_fold(cur, *self._prior, sse=sse0, grad=g0)
         s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
         s.update({'gcur': g0.double() if f32op else g0.clone(),
                   'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),

@@ -22,6 +22,7 @@ import torch
 
 from .. import _lib
 from .device_engine import DeviceEngine
+from .prior import fold_constants
 from .sgmcmc import SCHEDULES, check_sg_args
 
 
@@ -30,16 +31,18 @@ class DeviceSGHMC(DeviceEngine):
     (0, 1], default 0.1; 1 is SGLD), batch (rows per chain and step, drawn with replacement; None: all rows in order, a
     deterministic gradient), thin (every thin-th state is stored), schedule ('constant' | 'cyclic'), cycles and explore_frac
     (cyclic: number of cosine cycles over the run, and the head of each cycle that runs without noise), temperature (1: the
-    posterior; 0: no noise), plus the engine's seed / chain0 / use_graph / groups."""
+    posterior; 0: no noise), plus the engine's seed / chain0 / use_graph / groups and priorsigma (None: no prior; s: the Gaussian
+    weight prior N(0, s^2 I), folded into every minibatch call's SSE and gradient with the constants times Nb / N, so that the
+    update's N / Nb leaves it unscaled: the prior is exact, only the likelihood is estimated)."""
 
     def __init__(self, op, sigma, eta=1e-5, alpha=0.1, batch=None, thin=1, schedule='constant', cycles=1, explore_frac=0.0,
-                 temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None):
+                 temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None, priorsigma=None):
         check_sg_args(eta, alpha, batch, thin, schedule, cycles, explore_frac, temperature)
         self.eta, self.alpha = float(eta), float(alpha)
         self.batch = None if batch is None else int(batch)
         self.thin, self.schedule, self.cycles = int(thin), schedule, int(cycles)
         self.explore_frac, self.temperature = float(explore_frac), float(temperature)
-        super().__init__(op, sigma, seed, chain0, use_graph, groups)
+        super().__init__(op, sigma, seed, chain0, use_graph, groups, priorsigma)
 
     def _ngroups(self, C):
         if self.groups is None:
@@ -48,7 +51,8 @@ class DeviceSGHMC(DeviceEngine):
 
     def _clone(self, op, chain0):
         return DeviceSGHMC(op, self.sigma, self.eta, self.alpha, self.batch, self.thin, self.schedule, self.cycles,
-                           self.explore_frac, self.temperature, self.seed, chain0, self.use_graph, groups=1)
+                           self.explore_frac, self.temperature, self.seed, chain0, self.use_graph, groups=1,
+                           priorsigma=self.priorsigma)
 
     def _step(self, s, nmcmc, final=False):
         """Enqueue one inner step on the current stream: the gradient on the rows of slot s['par'], then the update (final: the
@@ -59,6 +63,8 @@ class DeviceSGHMC(DeviceEngine):
         rows = s['rows']
         self.op.sse_grad(s['theta'] if s['thop'] is None else s['thop'], row_idx=None if rows is None else rows[par],
                          out=(s['sse'], s['g']))
+        if s['prior'] is not None:                  # (lam, c0) x Nb / N: the update's N / Nb leaves the prior unscaled
+            self.op.prior_fold(s['theta'], *s['prior'], sse=s['sse'], grad=s['g'])
         _lib.check(self._L.qn_sg_step(
             s['theta'].data_ptr(), ptr(s['v']), s['g'].data_ptr(), self.op.qdt, s['sse'].data_ptr(), self.sigma, self.op.N,
             s['Nb'], self.eta, self.alpha, self.temperature, SCHEDULES.index(self.schedule), s['K'] or 0, self.explore_frac,
@@ -84,7 +90,8 @@ class DeviceSGHMC(DeviceEngine):
                       if store_chain else None,
              'lps': torch.empty(C, nmcmc + 1, dtype=f64, device=dev),
              'rows': None if self.batch is None else torch.empty(2, C, Nb, dtype=torch.int32, device=dev),
-             'step': torch.zeros(2, dtype=torch.int64, device=dev), 'par': 0, 'Nb': Nb, 'K': K}
+             'step': torch.zeros(2, dtype=torch.int64, device=dev), 'par': 0, 'Nb': Nb, 'K': K,
+             'prior': None if self.priorsigma is None else fold_constants(self.sigma, self.priorsigma, p, self.op.N, Nb)}
         if store_chain:
             s['chain'][:, 0] = cur
         if s['rows'] is not None:                                  # rows of step 0; every later step draws its successor's
@@ -128,7 +135,7 @@ class DeviceSGLD(DeviceSGHMC):
     """Stochastic-gradient Langevin dynamics: `DeviceSGHMC` with alpha = 1 (no momentum array)."""
 
     def __init__(self, op, sigma, eta=1e-5, batch=None, thin=1, schedule='constant', cycles=1, explore_frac=0.0,
-                 temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None):
+                 temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None, priorsigma=None):
         super().__init__(op, sigma, eta=eta, alpha=1.0, batch=batch, thin=thin, schedule=schedule, cycles=cycles,
                          explore_frac=explore_frac, temperature=temperature, seed=seed, chain0=chain0, use_graph=use_graph,
-                         groups=groups)
+                         groups=groups, priorsigma=priorsigma)

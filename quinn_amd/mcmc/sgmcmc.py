@@ -1,8 +1,9 @@
 """Stochastic-gradient MCMC (SGLD, Welling & Teh 2011; SGHMC, Chen et al. 2014; cyclical step size, Zhang et al. 2020): the
 contract of the device engines `DeviceSGLD` / `DeviceSGHMC` (qn_sg_rows / qn_sg_step, csrc/qn_sgmcmc.hip), restated in numpy.
 
-Target: the Gaussian likelihood with noise sigma and no prior, U(theta) = SSE(theta) / (2 sigma^2) + const, as every sampler of
-this package.  Inner step t of a chain with minibatch rows B_t (Nb rows drawn uniformly WITH replacement from the N data rows):
+Target: the Gaussian likelihood with noise sigma, U(theta) = SSE(theta) / (2 sigma^2) + const, as every sampler of this package
+(with `priorsigma` the engines fold a Gaussian weight prior into SSE and gradient beforehand, unscaled by N / Nb:
+`quinn_amd.mcmc.prior`).  Inner step t of a chain with minibatch rows B_t (Nb rows drawn uniformly WITH replacement from the N data rows):
 
     g   = (N / Nb) * d SSE_{B_t} / d theta / (2 sigma^2)          # unbiased estimate of the gradient of U
     eta = eta0                                                     schedule 'constant'

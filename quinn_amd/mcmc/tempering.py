@@ -12,8 +12,9 @@ scheme, Okabe et al. 2001), and a pair swaps its states iff
 with lp the untempered log-posteriors (a NaN or infinite lp never moves).  Each rung's chain leaves pi^beta_r invariant under
 both moves, so the cold chains (rung 0) sample the target itself while inheriting the hot rungs' barrier crossings.
 
-The target is the likelihood alone (no prior, as everywhere in `NN_MCMC`): beta scales the whole log-posterior, hot rungs of a
-network with flat directions can wander far, and `beta_min` is the caller's choice.  Not here: ladder adaptation, tempering of
+beta scales the whole log-posterior: the likelihood alone by default, where hot rungs of a network with flat directions can wander
+far, or likelihood and prior with `priorsigma` (`quinn_amd.mcmc.prior`: a hot rung's prior then has the bounded variance
+priorsigma^2 / beta); `beta_min` is the caller's choice.  Not here: ladder adaptation, tempering of
 AMCMC and of the SG samplers, host engines, thermodynamic integration.
 """
 import numpy as np

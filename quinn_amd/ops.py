@@ -443,6 +443,28 @@ class BatchedMLP:
         s, _, g = self._call(W, row_idx, False, True, out=out)
         return s, g
 
+    def prior_fold(self, W, lam, c0, sse=None, grad=None, sse_stride=1):
+        """Fold the Gaussian weight prior into the outputs of the forward / gradient call just made at W [C, p] float64
+        (qn_prior_fold, one launch on the current stream, in place): grad [C, p] float64 / float32 += (2 lam) W,
+        sse[c * sse_stride] += lam |W[c]|^2 + c0 (sse float64, [C] or [C, sse_stride]: column 0 receives the term).
+        `quinn_amd.mcmc.prior.fold_constants` gives (lam, c0)."""
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
+            raise ValueError("prior_fold: W is a contiguous float64 device tensor [C, p]")
+        C, p = W.shape
+        gdt = _lib.QN_F64
+        if grad is not None:
+            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
+                raise ValueError("prior_fold: grad is a contiguous float64 / float32 tensor of W's shape")
+            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
+        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
+                                sse.numel() != C * int(sse_stride)):
+            raise ValueError("prior_fold: sse is a contiguous float64 tensor of C * sse_stride entries")
+        if C == 0:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_prior_fold(W.data_ptr(), float(lam), float(c0), _ptr(grad), gdt, _ptr(sse), int(sse_stride),
+                                             C, p, _stream(self.device)), "qn_prior_fold")
+
     def sse_pred(self, W, row_idx=None):
         s, pr, _ = self._call(W, row_idx, True, False)
         return s, pr

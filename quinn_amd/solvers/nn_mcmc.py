@@ -5,9 +5,10 @@ Mirror of the reference's `NN_MCMC` (quinn/solvers/nn_mcmc.py:15-200): same cons
 `cmode`, `pdim`, `lpinfo`).  Build-only keyword extras (defaults = reference behaviour):
 `nchains`, `seeds` on `fit`; `device`, `dtype` on the constructor.
 
-logpost(w) = -[ 0.5*SSE(w)/sigma^2 + (N/2) log 2pi + N log sigma ]   (no prior,
+logpost(w) = -[ 0.5*SSE(w)/sigma^2 + (N/2) log 2pi + N log sigma ]   (no prior by default, as
 nn_mcmc.py:64 -> losses.py:197-200); SSE and dSSE/dw come from the HIP kernels, the scalar
-tail is applied here in float64.  With gradient observations (`fit(..., gtrn=, gradnoise=)`) a second Gaussian
+tail is applied here in float64.  `fit(..., priorsigma=s)` (build-only) adds the isotropic Gaussian weight prior
+log N(w; 0, s^2 I), normaliser included, on every engine (`quinn_amd.mcmc.prior`).  With gradient observations (`fit(..., gtrn=, gradnoise=)`) a second Gaussian
 likelihood term on the input Jacobian is added (host engine; `BatchedMLP.sobolev`).
 """
 import copy
@@ -26,6 +27,7 @@ from ..mcmc.device_mala import DeviceMALA
 from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
 from ..mcmc import diagnostics as diag
 from ..mcmc.tempering import check_temper_args, check_whole_ladders
+from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
@@ -86,14 +88,17 @@ class NN_MCMC(QUiNNBase):
             sys.exit()
 
     def logpost_batch(self, W, lpinfo=None):
-        """Log-posterior of every row of W `(C,p)`: numpy float64 `(C,)`."""
+        """Log-posterior of every row of W `(C,p)`: numpy float64 `(C,)` (with lparams['priorsigma'] set: the Gaussian weight
+        prior included)."""
         lpinfo = self.lpinfo if lpinfo is None else lpinfo
         self._check_ltype(lpinfo)
         op = self._operator(lpinfo)
         if lpinfo.get('gd') is not None:
             return self._logpost_grad_data(op, np.atleast_2d(W), lpinfo, False)[0]
         sse = op.sse(np.atleast_2d(W)).cpu().numpy()
-        return -neg_log_post_from_sse(sse, len(lpinfo['yd']), lpinfo['lparams']['sigma'])
+        lp = -neg_log_post_from_sse(sse, len(lpinfo['yd']), lpinfo['lparams']['sigma'])
+        ps = lpinfo['lparams'].get('priorsigma')
+        return lp if ps is None else lp + log_prior(W, ps)
 
     def logpostgrad_batch(self, W, lpinfo=None):
         """Gradient of the log-posterior for every row of W: numpy float64 `(C,p)`."""
@@ -104,19 +109,27 @@ class NN_MCMC(QUiNNBase):
             return self._logpost_grad_data(op, np.atleast_2d(W), lpinfo, True)[1]
         _, g = op.sse_grad(np.atleast_2d(W))
         sig = np.float64(lpinfo['lparams']['sigma'])
-        return -(0.5 * g.double().cpu().numpy() / sig ** 2)
+        glp = -(0.5 * g.double().cpu().numpy() / sig ** 2)
+        ps = lpinfo['lparams'].get('priorsigma')
+        return glp if ps is None else glp + grad_log_prior(W, ps)
 
     @staticmethod
     def _logpost_grad_data(op, W, lpinfo, want_grad):
         """(log-posterior (C,), its gradient (C, p) or None) with gradient observations, one `sobolev` call:
-        -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2) - N o d (log sigma_g + log(2 pi) / 2)."""
+        -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2) - N o d (log sigma_g + log(2 pi) / 2),
+        plus the Gaussian weight prior when lparams['priorsigma'] is set."""
         sig, sg = np.float64(lpinfo['lparams']['sigma']), np.float64(lpinfo['lparams']['sigma_g'])
         d, o = op.arch.dims[0], op.arch.dims[-1]
         cv, cg = -0.5 / sig ** 2, -0.5 / sg ** 2
         sse, gsse, g = op.sobolev(W, cv, cg, want_grad=want_grad)
         half = 0.5 * np.log(2 * np.float64(np.pi))
         lp = cv * sse.cpu().numpy() + cg * gsse.cpu().numpy() - op.N * o * (np.log(sig) + half) - op.N * o * d * (np.log(sg) + half)
-        return lp, (g.cpu().numpy() if want_grad else None)
+        glp = g.cpu().numpy() if want_grad else None
+        ps = lpinfo['lparams'].get('priorsigma')
+        if ps is not None:
+            lp = lp + log_prior(W, ps)
+            glp = glp + grad_log_prior(W, ps) if want_grad else None
+        return lp, glp
 
     def logpost(self, modelpars, lpinfo):
         """float: log-posterior of one flat weight vector (reference signature)."""
@@ -129,7 +142,7 @@ class NN_MCMC(QUiNNBase):
     # -- fit -------------------------------------------------------------------------------
     def fit(self, xtrn, ytrn, zflag=True, datanoise=0.05, nmcmc=6000, param_ini=None, sampler='amcmc',
             sampler_params=None, *, nchains=1, seeds=None, engine='host', gather='all', gather_chain=None, bfgs_jac=None,
-            diagnostics=False, diag_nburn=None, gtrn=None, gradnoise=None):
+            diagnostics=False, diag_nburn=None, gtrn=None, gradnoise=None, priorsigma=None):
         """Run MCMC over the flat weight vector.
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
@@ -183,8 +196,18 @@ class NN_MCMC(QUiNNBase):
             term, log-posterior -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2)
             - N o d (log sigma_g + log(2 pi) / 2) with gsse = sum (dM/dx - gtrn)^2; engine='host' only (the device engines'
             accept kernels take a bare SSE).
+            priorsigma: None (default) -- no prior, the reference's target; s > 0 -- the isotropic Gaussian weight prior
+            N(0, s^2 I) (`quinn_amd.mcmc.prior`), stored as lpinfo['lparams']['priorsigma'].  `logpost` / `logpostgrad` and
+            their batched forms then include log N(w; 0, s^2 I) (normaliser included) and -w / s^2, so the host samplers and
+            the `zflag` BFGS pre-fit (which becomes the MAP with the prior) need no change; engine='device' hands s to the
+            engine, which folds the prior into every SSE / gradient on the GPU (qn_prior_fold): 'logpost', 'maxpost' and
+            the MAP of every engine are those of the posterior with the prior, on every rung of a ladder (whose beta
+            tempers likelihood and prior alike: a hot rung's prior has variance s^2 / beta).  The SG samplers' prior is
+            exact, only their likelihood is a minibatch estimate.  One scalar s: no per-layer or ARD scales, no hyper-prior.
+            Anything but None or a finite s > 0 raises ValueError before any launch.
         """
         self.diagnostics = None
+        priorsigma = check_priorsigma(priorsigma)
         if sampler in DEVICE_ONLY and engine != 'device':
             raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host SG sampler)")
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
@@ -192,6 +215,8 @@ class NN_MCMC(QUiNNBase):
         assert xtrn.shape[0] == ntrn_
         self.lpinfo = {'model': None, 'xd': xtrn, 'yd': [y for y in ytrn], 'ltype': 'classical',
                        'lparams': {'sigma': datanoise}}
+        if priorsigma is not None:
+            self.lpinfo['lparams']['priorsigma'] = priorsigma
         if gtrn is not None:
             if engine == 'device':
                 raise NotImplementedError("gradient observations (gtrn) need engine='host': the device samplers' accept "
@@ -248,7 +273,7 @@ class NN_MCMC(QUiNNBase):
                                       use_graph=sampler_params.get('use_graph', False)).size
                 check_whole_ladders(R, hi - lo, lo)
                 nrounds = nmcmc // int(sampler_params.get('swap_every', 1))
-            eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, **sampler_params)
+            eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, priorsigma=priorsigma, **sampler_params)
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
             else:
