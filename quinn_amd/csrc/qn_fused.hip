@@ -1385,9 +1385,12 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
     (void)hipGetLastError();
     if (!want_grad) {
         fwd_fn kern = pick_fwd(H, a.act, padded_d(a.d), a.o);
+        int threads = H == HS ? NTS : WG;
         if (uses_i8(d, want_grad)) {
-            kern = qn_fused_i8_kernel(a.d, a.o, a.act);
-            lds_bytes = qn_fused_i8_lds_bytes(a.d, nhid);
+            kern = qn_fused_i8_kernel(a.d, a.o, a.act, nhid);
+            lds_bytes = qn_fused_i8_lds_bytes(a.d, nhid, a.act);
+            threads = qn_fused_i8_threads(a.d, nhid, a.act);
+            grid = dim3(qn_fused_grid(qn_fused_i8_grid_splits(a.d, nhid, a.act, a.nsplit), B));
 #ifdef QN_DEBUG_LDS_PAD
             if (const char* pad = getenv("QN_DEBUG_LDS_PAD")) lds_bytes += (size_t)atoi(pad);     // (occupancy experiments)
 #endif
@@ -1403,7 +1406,7 @@ int qn_fused_run(const qn_desc* d, int dtype, const void* W, const void* X, cons
         arrive = nullptr;                                   // A/B builds: the separate k_sum_partials launch
 #endif
         summed = arrive != nullptr;
-        hipLaunchKernelGGL(kern, grid, dim3(H == HS ? NTS : WG), lds_bytes, st, a, (const double*)W,
+        hipLaunchKernelGGL(kern, grid, dim3(threads), lds_bytes, st, a, (const double*)W,
                            (const double*)X, (const double*)Y, row_idx, (double*)pred, partial, arrive, sse);
     } else {
         bwd_fn kern = pick_bwd(H, nhid, d->act, bwd_dp(a.d, a.o), bwd_om(a.o));

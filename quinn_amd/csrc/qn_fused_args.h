@@ -117,10 +117,15 @@ qn_bwd_f64_fn qn_fused_bwd_o16_kernel(int H, int nhid, int act, int dp);
 
 // sliced int8-product forward for 64-wide tanh networks (qn_fused_i8.hip): same grid, block and partial-sum
 // conventions as k_fused_fwd_f64<64, 2, tanh, DP, 256>
-int qn_fused_i8_rows_per_iteration();       // data rows one workgroup covers per loop iteration
+int qn_fused_i8_rows_per_iteration();       // data rows the four waves of one row split cover per loop iteration
 bool qn_fused_i8_applies(int H, int nhid, int act, int d, int o);
-size_t qn_fused_i8_lds_bytes(int d, int nhid);
-qn_fwd_fn qn_fused_i8_kernel(int d, int o, int act);
+// (tanh networks of up to 3 hidden layers run as workgroups of 8 waves that take two row splits each: block size, LDS bytes
+// and the number of splits the grid is built from depend on the network; plan, partials and arrivals stay per split)
+bool qn_fused_i8_pairs(int d, int nhid, int act);
+size_t qn_fused_i8_lds_bytes(int d, int nhid, int act);
+int qn_fused_i8_threads(int d, int nhid, int act);
+int qn_fused_i8_grid_splits(int d, int nhid, int act, int nsplit);
+qn_fwd_fn qn_fused_i8_kernel(int d, int o, int act, int nhid);
 
 // sliced int8-product forward + backward for 64-wide tanh networks (qn_fused_bwd_i8.hip): grid, partial-sum and gradient-slab
 // conventions of k_fused_bwd_f64<64, NH, 4>; `flags` [B][nsplit]: (chain, split)s that left the fast path (the caller

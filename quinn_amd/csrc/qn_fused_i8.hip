@@ -24,7 +24,7 @@
 // k-slots), C/D: lane (q, c) holds features 16 t + 4 q + r (r = 0..3) of row c.  The k-slot <-> feature map is free
 // as long as both operands use it: byte j of lane group q is feature 16 (j >> 2) + 4 q + (j & 3), which makes the four
 // results of output tile t exactly bytes 4 t .. 4 t + 3 of the NEXT layer's B operand: activations go
-// accumulator -> float64 (tanh) -> digits -> operand without leaving the lane.  First layer (d <= 8: DP = 2, 4 or 8 padded input columns) and last layer
+// accumulator -> float64 (tanh) -> digits -> operand without leaving the lane.  First layer (d <= 8: DP = 2, 4 or 8 padded input columns; d = 1 in the 8-wave form: DP = 1) and last layer
 // (o <= 4) on the VALU as in k_fused_fwd_f64; the last hidden layer's outputs are consumed as float64 (no slicing).
 //
 // Anything that could make a NaN / inf (a weight or input that is not finite and < 2^500) leaves the fast path: the
@@ -58,7 +58,9 @@ namespace {
 __device__ __forceinline__ bool bounded20(double v) { return (unsigned)(__double2hiint(v) & 0x7fffffff) < 0x41300000u; }
 __device__ __forceinline__ bool bounded100(double v) { return (unsigned)(__double2hiint(v) & 0x7fffffff) < 0x46300000u; }
 
-template <int DP, int LMIN, bool UNB = false>
+// NW waves stage together (4, or the 8 of the PAIR form): a thread takes 16 / NW items of four weights per matrix; every
+// weight is sliced on its own, so the image does not depend on NW.  TAB512: the tanh(n / 512) table instead of tanh(n / 64).
+template <int DP, int LMIN, bool UNB = false, int NW = 4, bool TAB512 = false>
 __device__ __forceinline__ int stage(double* __restrict__ lds, unsigned char* __restrict__ wq, double* __restrict__ tanh_tab,
                                      const double* __restrict__ Wb, const FusedArgs& a, long long* stamps = nullptr) {
     int bad = 0;
@@ -73,31 +75,34 @@ __device__ __forceinline__ int stage(double* __restrict__ lds, unsigned char* __
     // plane (k-slot map of the header), the 16 lanes of a DPP row take one matrix row: the row's largest exponent is 4
     // DPP steps, the digits come out of slice4 already packed, 6 ds_write_b32 per item (byte stores of single digits
     // were 4-way bank conflicts and, with a ds_bpermute row maximum, 19 % of the kernel)
-    auto load_matrix = [&](int layer, double (&v)[4][4]) {
+    constexpr int NT = 64 * NW, U = 16 / NW, RU = H / U;                  // threads, items per thread, rows between a thread's items
+    auto load_matrix = [&](int layer, double (&v)[U][4]) {
         const double* Wg = Wb + gHH + (int64_t)(layer - 1) * (H * H + nb * H);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int row = 16 * u + 4 * wave + (lane >> 4);
+        for (int u = 0; u < U; ++u) {
+            const int row = RU * u + 4 * wave + (lane >> 4);
             const double2* src = reinterpret_cast<const double2*>(Wg + row * H + 16 * m4 + 4 * g4);
             const double2 v01 = src[0], v23 = src[1];
             v[u][0] = v01.x; v[u][1] = v01.y; v[u][2] = v23.x; v[u][3] = v23.y;
         }
     };
     // ---- issue: first hidden matrix, thin pieces, table
-    double vA[4][4], vB[4][4];                                            // (two named sets: a runtime-indexed array would live in scratch)
+    double vA[U][4], vB[U][4];                                            // (two named sets: a runtime-indexed array would live in scratch)
     load_matrix(1, vA);
-    constexpr int TPT = (QN_TANH_TAB64_N + WGT - 1) / WGT;
+    constexpr int TABN = TAB512 ? QN_TANH_TAB512_N : QN_TANH_TAB64_N;
+    const double* tab_g = TAB512 ? qn_tanh_table512_g : qn_tanh_table64_g;
+    constexpr int TPT = (TABN + NT - 1) / NT;
     double tt[TPT];
 #pragma unroll
-    for (int k = 0; k < TPT; ++k) tt[k] = tid + k * WGT < QN_TANH_TAB64_N ? qn_tanh_table64_g[tid + k * WGT] : 0.0;
-    constexpr int W0PT = (H * DP + WGT - 1) / WGT;                         // 1
+    for (int k = 0; k < TPT; ++k) tt[k] = tid + k * NT < TABN ? tab_g[tid + k * NT] : 0.0;
+    constexpr int W0PT = (H * DP + NT - 1) / NT;                           // 1 (DP = 8 on 4 waves: 2)
     double w0v[W0PT], wlv, b0v = 0.0, blv = 0.0;
 #pragma unroll
     for (int k = 0; k < W0PT; ++k) {
-        const int e = tid + k * WGT, j = e / DP, kk = e % DP;
+        const int e = tid + k * NT, j = e / DP, kk = e % DP;
         w0v[k] = (e < H * DP && kk < d) ? Wb[j * d + kk] : 0.0;
     }
-    wlv = tid < o * H ? Wb[gWl + tid] : 0.0;                               // (OMAX * H = WGT)
+    wlv = tid < o * H ? Wb[gWl + tid] : 0.0;                               // (OMAX * H = 256 threads)
     if (tid < H && nb) b0v = Wb[gb0 + tid];
     if (tid < OMAX && tid < o && nb) blv = Wb[gbl + tid];
 #ifdef QN_FWD8_STAMPS
@@ -106,12 +111,12 @@ __device__ __forceinline__ int stage(double* __restrict__ lds, unsigned char* __
     // ---- consume
 #pragma unroll
     for (int k = 0; k < TPT; ++k)
-        if (tid + k * WGT < QN_TANH_TAB64_N) tanh_tab[tid + k * WGT] = tt[k];
+        if (tid + k * NT < TABN) tanh_tab[tid + k * NT] = tt[k];
 #pragma unroll
     for (int k = 0; k < W0PT; ++k)
-        if (tid + k * WGT < H * DP) lds[tid + k * WGT] = chk(w0v[k]);
-    lds[lWl + tid] = chk(wlv);
-    if (tid < H) lds[lb0 + tid] = chk(b0v);
+        if (tid + k * NT < H * DP) lds[DP == 1 ? 2 * tid : tid + k * NT] = chk(w0v[k]);      // (DP = 1: {W0, b0} pairs)
+    if (tid < OMAX * H) lds[lWl + tid] = chk(wlv);
+    if (tid < H) lds[DP == 1 ? 2 * tid + 1 : lb0 + tid] = chk(b0v);
     if (tid < OMAX) lds[lbl + tid] = chk(blv);
 #ifdef QN_FWD8_STAMPS
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -119,16 +124,16 @@ __device__ __forceinline__ int stage(double* __restrict__ lds, unsigned char* __
 #endif
     // (step-major over the thread's four items: exponents, row maxima, scaling, digits, stores -- written item by item the
     // compiler keeps each item's dependent chain together and a matrix took 2.3 us per workgroup, three times its issue time)
-    auto slice_matrix = [&](int layer, const double (&v)[4][4]) {
+    auto slice_matrix = [&](int layer, const double (&v)[U][4]) {
         const double* Wg = Wb + gHH + (int64_t)(layer - 1) * (H * H + nb * H);
         unsigned char* plane = wq + (layer - 1) * LAYER_BYTES;
         double* sb = lds + lsb + (layer - 1) * 2 * H;
-        double bias[4];
+        double bias[U];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) bias[u] = (q16 == 0 && nb) ? Wg[H * H + 16 * u + 4 * wave + (lane >> 4)] : 0.0;
-        unsigned ex[4];
+        for (int u = 0; u < U; ++u) bias[u] = (q16 == 0 && nb) ? Wg[H * H + RU * u + 4 * wave + (lane >> 4)] : 0.0;
+        unsigned ex[U];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < U; ++u) {
             ex[u] = 0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -136,25 +141,25 @@ __device__ __forceinline__ int stage(double* __restrict__ lds, unsigned char* __
                 ex[u] = max(ex[u], ((unsigned)__double2hiint(v[u][r]) & 0x7fffffffu) >> 20);
             }
         }
-        row16_max_u32_n<4>(ex);
-        int e[4];
-        double an[4][4];
+        row16_max_u32_n<U>(ex);
+        int e[U];
+        double an[U][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < U; ++u) {
             // 2^e > every |W_ji| of the row, from the largest biased exponent field E: |w| < 2^(E - 1022)
             e[u] = (int)ex[u] - 1022;
             bad |= e[u] > I8_MAX_WEIGHT_EXP;                           // (an outlier weight: see qn_i8_slice.h)
             e[u] = e[u] < -900 ? -900 : e[u];                          // (all-zero / denormal rows: any scale will do)
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+        for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int r = 0; r < 4; ++r) an[u][r] = ldexp(v[u][r], -e[u]);    // exact, |an| < 1
-        int S[4][NS];
-        slice4_n<4>(an, S);
+        int S[U][NS];
+        slice4_n<U>(an, S);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int row = 16 * u + 4 * wave + (lane >> 4);
+        for (int u = 0; u < U; ++u) {
+            const int row = RU * u + 4 * wave + (lane >> 4);
             unsigned char* dst = plane + row * H + 16 * (g4 ^ slot_swz(row)) + 4 * m4;
 #pragma unroll
             for (int k = 0; k < NS; ++k) *reinterpret_cast<int*>(dst + k * SLICE_BYTES) = S[u][k];
@@ -198,8 +203,8 @@ __device__ __noinline__ double slow_tile(int Nb, int d, int o, int nhid, int has
     double sse = 0.0;
     for (int n = nbase; n < nbase + 16 * G && n < Nb; ++n) {
         const int64_t rr = row_idx ? (int64_t)row_idx[(int64_t)b * Nb + n] : (int64_t)n;
-        double z = lds[lb0 + lane];
-        for (int k = 0; k < d; ++k) z = fma(lds[lane * DP + k], X[rr * d + k], z);
+        double z = lds[DP == 1 ? 2 * lane + 1 : lb0 + lane];
+        for (int k = 0; k < d; ++k) z = fma(lds[DP == 1 ? 2 * lane : lane * DP + k], X[rr * d + k], z);
         auto actf = [](double v) { return ACT == QN_ACT_TANH ? qn_tanh_f64(v) : ACT == QN_ACT_RELU ? qn_relu<double>(v) : v; };
         double act = actf(z);
         for (int layer = 1; layer < nhid; ++layer) {
@@ -223,13 +228,48 @@ __device__ __noinline__ double slow_tile(int Nb, int d, int o, int nhid, int has
     return sse;
 }
 
+// qn_tanh_f64_tab512 (qn_tanh512.h) for four values, step-major; `magic52`: 1.5 2^52 in a register pair the compiler cannot see
+// through (a known addend makes hipcc emit v_fmac_f64 behind moves: the hidden epilogue's note)
+__device__ __forceinline__ void tanh512_x4(const double (&z)[4], double (&av)[4], const double* __restrict__ tab, double magic52) {
+    double ax[4], zm[4], Tt[4], bb[4], b2[4], tb[4], e[4], den[4], w[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) asm("v_min_f64 %0, |%1|, %2" : "=v"(ax[r]) : "v"(z[r]), "s"(20.0));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) asm("v_fma_f64 %0, %1, %2, %3" : "=v"(zm[r]) : "v"(ax[r]), "s"(512.0), "v"(magic52));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Tt[r] = tab[__double2loint(zm[r])];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const double nf = zm[r] - magic52; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(bb[r]) : "v"(nf), "s"(-0.001953125), "v"(ax[r])); }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b2[r] = bb[r] * bb[r];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b2[r] = bb[r] * b2[r];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tb[r] = fma(b2[r], -3.33333333333333333e-01, bb[r]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { e[r] = Tt[r] * tb[r]; den[r] = fma(-Tt[r], Tt[r], 1.0); }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { w[r] = fma(-tb[r], e[r], tb[r]); e[r] = e[r] * e[r]; }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w[r] = fma(w[r], e[r], w[r]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) av[r] = __builtin_copysign(fma(den[r], w[r], Tt[r]), z[r]);
+}
+
 // ACT = tanh: activations in [-1, 1], sliced with the fixed scale 2^-46 inside each tile's epilogue.  ACT = relu / identity
 // (round 4; the reference's DEFAULT activation is relu, quinn/nns/mlp.py:23): activations are unbounded, so every data row gets
 // its own scale 2^f_n > max_j |a_j(n)| over the layer's 64 features -- a layer's 16 outputs per lane stay float64 until its last
 // tile is done (row maximum in-lane over the 4 tiles, then across the 4 lane groups), are sliced then (slice_rows), and the next
 // layer's integer sums are multiplied by 2^f_n.  Same norm-wise 47-bit bound per row; no tanh table, no tiny-activation rule.
-template <int DP, int LMIN, int OM, int ACT = QN_ACT_TANH>
-__global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const double* __restrict__ W,
+//
+// PAIR (tanh networks whose image leaves room for the large table): workgroups of 8 waves, one per CU.  A workgroup takes two
+// adjacent row splits of one chain -- waves 0-3 split 2k, waves 4-7 split 2k + 1 -- and all 8 waves stage the chain's image
+// ONCE: half the weight fetches and half the slicing per wave, and the LDS of the second image holds tanh(n / 512)
+// (qn_tanh_f64_tab512: two vector instructions per element fewer).  Row plan, partial sums and arrivals are per split, as in
+// the 4-wave form; with an odd number of splits the upper half of the last workgroup has no rows, but stages and takes
+// every barrier.
+template <int DP, int LMIN, int OM, int ACT = QN_ACT_TANH, bool PAIR = false>
+__global__ __launch_bounds__(PAIR ? 2 * WGT : WGT, PAIR ? 1 : 2) void k_fused_fwd_i8(FusedArgs a, const double* __restrict__ W,
                                                         const double* __restrict__ X, const double* __restrict__ Y,
                                                         const int32_t* __restrict__ row_idx, double* __restrict__ pred_out,
                                                         double* __restrict__ partial, unsigned long long* __restrict__ arrive,
@@ -237,17 +277,23 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NLEV = 2 * (NS - 1) - LMIN + 1;       // levels LMIN .. 10
     constexpr bool TANH = ACT == QN_ACT_TANH;
+    static_assert(TANH || !PAIR, "the 8-wave form is built for tanh networks");
+    static_assert(DP != 1 || PAIR, "the one-column first layer uses the tanh(n / 512) table of the 8-wave form");
+    constexpr int NW = PAIR ? 8 : 4, TABD = PAIR ? TANH_TAB512 : TANH_TAB;
     double* lds = reinterpret_cast<double*>(smem);
     const int NH = a.nhid, d = a.d, o = a.o;
     int b, split;
-    if (!qn_fused_wg(a.nsplit, a.B, &b, &split)) return;
+    if (!qn_fused_wg(PAIR ? (a.nsplit + 1) / 2 : a.nsplit, a.B, &b, &split)) return;     // (the whole workgroup)
+    const int wave = threadIdx.x >> 6, half = PAIR ? wave >> 2 : 0, w4 = wave & 3;      // w4: the wave inside its split
+    if constexpr (PAIR) split = 2 * split + half;
+    const bool active = split < a.nsplit;                       // (false: the upper half behind an odd number of splits)
     const int offb0 = H * DP, offWl = offb0 + H, offbl = offWl + OMAX * H, offred = offbl + OMAX, offsb = thin_doubles(DP);
     double* tanh_tab = lds + ((offsb + (NH - 1) * 2 * H + 1) & ~1);
-    double* scratch = tanh_tab + ((TANH_TAB + 1) & ~1);
-    unsigned char* wq = reinterpret_cast<unsigned char*>(lds + head_doubles(DP, NH));
+    double* scratch = tanh_tab + ((TABD + 1) & ~1);
+    unsigned char* wq = reinterpret_cast<unsigned char*>(lds + head_doubles(DP, NH, TABD, NW));
     double* red = lds + offred;
     const double* Wb = W + (int64_t)b * a.p;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int q = lane >> 4, c = lane & 15;
 #ifdef QN_I8_STAGGER
     // experiment: break the lockstep of the two waves of a SIMD (same program, same start) by delaying the odd wave slot
@@ -262,7 +308,7 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
     int xbad_n = 0;
     auto fetch = [&](int it) {
         xbad_n = 0;
-        const int nbase = split * a.rows_per_split + (it * (WGT / 64) + wave) * 16 * G;
+        const int nbase = split * a.rows_per_split + (it * (WGT / 64) + w4) * 16 * G;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int n = nbase + 16 * g + c;
@@ -293,14 +339,16 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
     fetch(0);                                                   // (in flight during the staging)
 #ifdef QN_FWD8_STAMPS
     long long sst[4] = {0, 0, 0, 0};
-    const int sbad = stage<DP, LMIN, !TANH>(lds, wq, tanh_tab, Wb, a, sst);
+    const int sbad = stage<DP, LMIN, !TANH, NW, PAIR>(lds, wq, tanh_tab, Wb, a, sst);
     sst[3] = __builtin_amdgcn_s_memrealtime();                           // second matrix sliced
-    const bool w_bad = block_or(sbad, red + 6);
+    const bool w_bad = block_or(sbad, red + 8);
     const long long rt1 = __builtin_amdgcn_s_memrealtime();
 #else
-    const bool w_bad = block_or(stage<DP, LMIN, !TANH>(lds, wq, tanh_tab, Wb, a), red + 6);
+    // (the flag has a slot of its own: a wave without rows writes its red[] slot while others may still read the flag)
+    const bool w_bad = block_or(stage<DP, LMIN, !TANH, NW, PAIR>(lds, wq, tanh_tab, Wb, a), red + 8);
 #endif
-    for (int it = 0; it < a.iters; ++it) {
+    const int iters = active ? a.iters : 0;
+    for (int it = 0; it < iters; ++it) {
         double xk[G][DP], yk[G][OM];
         int nrow[G];
         bool valid[G];
@@ -314,10 +362,10 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
             for (int qo = 0; qo < OM; ++qo) yk[g][qo] = yn[g][qo];
         }
         const bool exceptional = w_bad || __any(xbad_n);
-        if (it + 1 < a.iters) fetch(it + 1);
+        if (it + 1 < iters) fetch(it + 1);
         if (exceptional) {                                              // wave-uniform
             sse += slow_tile<DP, ACT>(a.Nb, a.d, a.o, a.nhid, a.has_bias, lds, scratch + 128 * wave, Wb, X, Y, row_idx,
-                                 split * a.rows_per_split + (it * (WGT / 64) + wave) * 16 * G, b, pred_out);
+                                 split * a.rows_per_split + (it * (WGT / 64) + w4) * 16 * G, b, pred_out);
             continue;
         }
         // ---- first layer (VALU): a_1 = tanh(W0 x + b0), sliced straight into the B operand
@@ -365,17 +413,30 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 double av[4];
+                if constexpr (DP == 1) {
+                    // one input column: {W0, b0} as one 16-byte read and one fma per feature, then the tanh step-major over the
+                    // tile's four elements (as the hidden epilogue: element-major the results travel through moves)
+                    double z1[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = 16 * t + 4 * q + r;
-                    double z = lds[offb0 + j];
+                    for (int r = 0; r < 4; ++r) {
+                        const double2 wb = *reinterpret_cast<const double2*>(lds + 2 * (16 * t + 4 * q + r));
+                        z1[r] = fma(wb.x, xk[g][0], wb.y);
+                    }
+                    tanh512_x4(z1, av, tanh_tab, magic52);
+                } else {
 #pragma unroll
-                    for (int k = 0; k < DP; ++k) z = fma(lds[j * DP + k], xk[g][k], z);
-                    if constexpr (TANH) av[r] = qn_tanh_f64_tab64(z, tanh_tab);
-                    else {
-                        av[r] = ACT == QN_ACT_RELU ? fmax(z, 0.0) : z;  // (finite here: unbounded weights / inputs took the plain loop)
-                        Vr[g][t][r] = av[r];
-                        amax[g] = fmax(amax[g], fabs(av[r]));
+                    for (int r = 0; r < 4; ++r) {
+                        const int j = 16 * t + 4 * q + r;
+                        double z = lds[offb0 + j];
+#pragma unroll
+                        for (int k = 0; k < DP; ++k) z = fma(lds[j * DP + k], xk[g][k], z);
+                        if constexpr (PAIR) av[r] = qn_tanh_f64_tab512(z, tanh_tab);
+                        else if constexpr (TANH) av[r] = qn_tanh_f64_tab64(z, tanh_tab);
+                        else {
+                            av[r] = ACT == QN_ACT_RELU ? fmax(z, 0.0) : z;  // (finite here: unbounded weights / inputs took the plain loop)
+                            Vr[g][t][r] = av[r];
+                            amax[g] = fmax(amax[g], fabs(av[r]));
+                        }
                     }
                 }
                 if constexpr (TANH) {
@@ -418,16 +479,19 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
                             const v4i (&B)[NS], const double* sbt, const double* wlt, int (&S)[NS], double (&prt)[OM], double rsg,
                             double (&avo)[4]) {
             constexpr bool LAST = decltype(last_tag)::value, NEXT = decltype(next_tag)::value;
-            constexpr int NSTAGE = 20;
+            // (PAIR: the tail of qn_tanh_f64_tab512 -- stage 7 is one instruction and stage 11 does not exist: 19 stages)
+            constexpr int NSTAGE = PAIR ? 19 : 20;
             v4i Af[NS];
             double2 sc[4];
             double ts[4], z[4], ax[4], zm[4], Tt[4], bb[4], b2[4], pp[4], tb[4], num[4], den[4], y0[4], e0[4], av[4];
             int lo[4], hi[4], p01, q01, p23, q23, r01, r23;
             auto stage = [&](auto st_tag) {
-                constexpr int st = decltype(st_tag)::value;                // (a compile-time stage index: every register index below is static)
+                constexpr int sti = decltype(st_tag)::value;               // (a compile-time stage index: every register index below is static)
+                constexpr int st = (PAIR && sti >= 11) ? sti + 1 : sti;    // the stage's label in the list below
                 if constexpr (NEXT) {
                     // the next tile's products, dealt out in proportion to the vector work of the stages (16 cycles each)
-                    constexpr int from = st ? stage_quota(st - 1, NPROD) : 0, upto = stage_quota(st, NPROD);
+                    constexpr int from = sti ? (PAIR ? stage_quota19(sti - 1, NPROD) : stage_quota(sti - 1, NPROD)) : 0;
+                    constexpr int upto = PAIR ? stage_quota19(sti, NPROD) : stage_quota(sti, NPROD);
 #pragma unroll
                     for (int k = 0; k < NPROD; ++k)
                         if (k >= from && k < upto) issue_product<LMIN>(k, accn, Af, B);
@@ -455,12 +519,14 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
                         asm("v_min_f64 %0, |%1|, %2" : "=v"(ax[r]) : "v"(z[r]), "s"(20.0));
                         // (one v_fma_f64 with the addend in an opaque register pair: for a known constant hipcc emits v_fmac_f64
                         // behind moves that re-materialise it -- 142 vector instructions fewer per 16 rows, +0.9 % A/B in one call)
-                        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(zm[r]) : "v"(ax[r]), "s"(64.0), "v"(magic52));
+                        if constexpr (PAIR) asm("v_fma_f64 %0, %1, %2, %3" : "=v"(zm[r]) : "v"(ax[r]), "s"(512.0), "v"(magic52));
+                        else asm("v_fma_f64 %0, %1, %2, %3" : "=v"(zm[r]) : "v"(ax[r]), "s"(64.0), "v"(magic52));
                         break;
                     case 5:
                         if constexpr (!TANH) break;
                         Tt[r] = tanh_tab[__double2loint(zm[r])];
-                        { const double nf_ = zm[r] - magic52; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(bb[r]) : "v"(nf_), "s"(-0.015625), "v"(ax[r])); }
+                        if constexpr (PAIR) { const double nf_ = zm[r] - magic52; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(bb[r]) : "v"(nf_), "s"(-0.001953125), "v"(ax[r])); }
+                        else { const double nf_ = zm[r] - magic52; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(bb[r]) : "v"(nf_), "s"(-0.015625), "v"(ax[r])); }
                         break;
                     case 6:
                         if constexpr (!TANH) break;
@@ -468,12 +534,13 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
                         break;
                     case 7:
                         if constexpr (!TANH) break;
-                        pp[r] = fma(b2[r], 1.33333333333333333e-01, -3.33333333333333333e-01);
+                        if constexpr (!PAIR) pp[r] = fma(b2[r], 1.33333333333333333e-01, -3.33333333333333333e-01);
                         b2[r] = bb[r] * b2[r];
                         break;
                     case 8:
                         if constexpr (!TANH) break;
-                        tb[r] = fma(b2[r], pp[r], bb[r]);
+                        if constexpr (PAIR) tb[r] = fma(b2[r], -3.33333333333333333e-01, bb[r]);      // b - b^3 / 3
+                        else tb[r] = fma(b2[r], pp[r], bb[r]);
                         break;
                     // (qn_tanh_f64_tab64 of qn_math.h, reciprocal-free tail: T + (1 - T^2) tb (1 - e)(1 + e^2 + e^4), e = T tb)
                     case 9:
@@ -492,7 +559,7 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
                         break;
                     case 12:
                         if constexpr (!TANH) break;
-                        y0[r] = fma(y0[r], e0[r], y0[r]);             // u
+                        y0[r] = fma(y0[r], e0[r], y0[r]);             // u (PAIR: e0 = e^2, stage 11 is skipped)
                         break;
                     case 13:
                         if constexpr (!TANH) break;
@@ -599,7 +666,7 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
         hidden_layer(std::true_type{}, NH - 1);
         if (redo) {                                                     // wave-uniform; rare
             sse += slow_tile<DP, ACT>(a.Nb, a.d, a.o, a.nhid, a.has_bias, lds, scratch + 128 * wave, Wb, X, Y, row_idx,
-                                 split * a.rows_per_split + (it * (WGT / 64) + wave) * 16 * G, b, pred_out);
+                                 split * a.rows_per_split + (it * (WGT / 64) + w4) * 16 * G, b, pred_out);
             continue;
         }
         // ---- last layer: finish the dot over the four lane groups, residual, SSE
@@ -633,7 +700,9 @@ __global__ __launch_bounds__(WGT, 2) void k_fused_fwd_i8(FusedArgs a, const doub
         (void)st0;
     }
 #endif
-    if (threadIdx.x < 64) qn_sse_finish(partial, arrive, sse_out, b, split, a.nsplit, (red[0] + red[1]) + (red[2] + red[3]));
+    // (each half sums its own four slots and arrives for its own split: the SSE of a split does not depend on the form)
+    const double* rh = red + 4 * half;
+    if (w4 == 0 && active) qn_sse_finish(partial, arrive, sse_out, b, split, a.nsplit, (rh[0] + rh[1]) + (rh[2] + rh[3]));
 }
 
 }  // namespace
@@ -648,20 +717,40 @@ bool qn_fused_i8_applies(int Hh, int nhid, int act, int d, int o) {
     if (act != QN_ACT_TANH) return false;                      // A/B builds: relu / identity on the float64-MFMA kernel
 #endif
     if (act != QN_ACT_TANH && nhid > 15) return false;         // (the overflow bound of the unbounded activations: stage())
-    return qn_fused_i8_lds_bytes(d, nhid) <= 160 * 1024;
+    return qn_fused_i8_lds_bytes(d, nhid, act) <= 160 * 1024;
 }
-size_t qn_fused_i8_lds_bytes(int d, int nhid) {
-    const int dp = d <= 2 ? 2 : d <= 4 ? 4 : 8;
-    return sizeof(double) * (size_t)head_doubles(dp, nhid) + (size_t)(nhid - 1) * LAYER_BYTES;
+#ifdef QN_I8_NO_DP1
+constexpr bool kDp1 = false;                                   // A/B builds: d = 1 on the two-column first layer
+#else
+constexpr bool kDp1 = true;
+#endif
+static int i8_dp(int d, bool pair) { return (kDp1 && pair && d == 1) ? 1 : d <= 2 ? 2 : d <= 4 ? 4 : 8; }     // (DP = 1: built for the 8-wave form)
+static size_t i8_image_bytes(int d, int nhid, bool pair) {
+    return sizeof(double) * (size_t)head_doubles(i8_dp(d, pair), nhid, pair ? TANH_TAB512 : TANH_TAB, pair ? 8 : 4) + (size_t)(nhid - 1) * LAYER_BYTES;
 }
-template <int ACT>
+// the 8-wave form (one image per CU, tanh(n / 512) table): tanh networks of up to 3 hidden layers -- beyond that image and
+// table do not fit the CU's 160 KB together, and the network runs in the 4-wave form as every relu / identity network does
+bool qn_fused_i8_pairs(int d, int nhid, int act) {
+#ifdef QN_I8_NO_PAIR
+    return false;                                              // A/B builds: every network in the 4-wave form
+#endif
+    return act == QN_ACT_TANH && i8_image_bytes(d, nhid, true) <= 160 * 1024;
+}
+size_t qn_fused_i8_lds_bytes(int d, int nhid, int act) { return i8_image_bytes(d, nhid, qn_fused_i8_pairs(d, nhid, act)); }
+int qn_fused_i8_threads(int d, int nhid, int act) { return qn_fused_i8_pairs(d, nhid, act) ? 2 * WGT : WGT; }
+// row splits as the grid sees them: the 8-wave form takes two splits per workgroup
+int qn_fused_i8_grid_splits(int d, int nhid, int act, int nsplit) { return qn_fused_i8_pairs(d, nhid, act) ? (nsplit + 1) / 2 : nsplit; }
+template <int ACT, bool PAIR = false>
 static qn_fwd_fn pick_i8(int d, int o) {
     // (5..8 inputs, round 4: the first layer is a VALU dot over DP padded input columns)
-    if (d > 4) return o > 1 ? k_fused_fwd_i8<8, QN_I8_LMIN, OMAX, ACT> : k_fused_fwd_i8<8, QN_I8_LMIN, 1, ACT>;
-    if (o > 1) return d <= 2 ? k_fused_fwd_i8<2, QN_I8_LMIN, OMAX, ACT> : k_fused_fwd_i8<4, QN_I8_LMIN, OMAX, ACT>;
-    return d <= 2 ? k_fused_fwd_i8<2, QN_I8_LMIN, 1, ACT> : k_fused_fwd_i8<4, QN_I8_LMIN, 1, ACT>;
+    if constexpr (PAIR)
+        if (kDp1 && d == 1) return o > 1 ? k_fused_fwd_i8<1, QN_I8_LMIN, OMAX, ACT, PAIR> : k_fused_fwd_i8<1, QN_I8_LMIN, 1, ACT, PAIR>;
+    if (d > 4) return o > 1 ? k_fused_fwd_i8<8, QN_I8_LMIN, OMAX, ACT, PAIR> : k_fused_fwd_i8<8, QN_I8_LMIN, 1, ACT, PAIR>;
+    if (o > 1) return d <= 2 ? k_fused_fwd_i8<2, QN_I8_LMIN, OMAX, ACT, PAIR> : k_fused_fwd_i8<4, QN_I8_LMIN, OMAX, ACT, PAIR>;
+    return d <= 2 ? k_fused_fwd_i8<2, QN_I8_LMIN, 1, ACT, PAIR> : k_fused_fwd_i8<4, QN_I8_LMIN, 1, ACT, PAIR>;
 }
-qn_fwd_fn qn_fused_i8_kernel(int d, int o, int act) {
+qn_fwd_fn qn_fused_i8_kernel(int d, int o, int act, int nhid) {
+    if (qn_fused_i8_pairs(d, nhid, act)) return pick_i8<QN_ACT_TANH, true>(d, o);
     return act == QN_ACT_RELU ? pick_i8<QN_ACT_RELU>(d, o) : act == QN_ACT_IDENTITY ? pick_i8<QN_ACT_IDENTITY>(d, o) : pick_i8<QN_ACT_TANH>(d, o);
 }
 

@@ -25,11 +25,14 @@ constexpr int LAYER_BYTES = NS * SLICE_BYTES;       // 24 KB
 constexpr double kMagic = 6755399441055744.0 + 551911719040.0;     // 1.5 * 2^52 + 0x8080808080 (exact)
 constexpr int TANH_TAB = QN_TANH64_LDS_DOUBLES;       // tanh(n / 64): the absolute-accuracy activation (qn_math.h)
 
-// LDS image, doubles first: W0 [64][DP] | b0 [64] | Wl [4][64] | bl [4] | red [8] | sb (NH-1) x [64][2] {scale, bias} |
-// tanh table | slow-path scratch 4 x 128 | then bytes: (NH-1) x 6 digit planes
-__host__ __device__ constexpr int thin_doubles(int dp) { return H * dp + H + OMAX * H + OMAX + 8; }
-__host__ __device__ constexpr int head_doubles(int dp, int nhid) {
-    return ((thin_doubles(dp) + (nhid - 1) * 2 * H + 1) & ~1) + ((TANH_TAB + 1) & ~1) + 4 * 128;
+// LDS image of the fused forward (qn_fused_i8.hip), doubles first: W0 [64][DP] | b0 [64] (DP = 1: {W0, b0} pairs [64][2]) |
+// Wl [4][64] | bl [4] | red [8] (one SSE slot per wave) | flag [2] (block_or) | sb (NH-1) x [64][2] {scale, bias} | tanh table
+// (`tab` doubles: tanh(n / 64) in the 4-wave form, tanh(n / 512) in the 8-wave form) | slow-path scratch `nw` x 128 (one per
+// wave) | then bytes: (NH-1) x 6 digit planes.  The 8-wave form stages ONE image per workgroup = per CU for two row splits.
+constexpr int TANH_TAB512 = QN_TANH_TAB512_N + 1;
+__host__ __device__ constexpr int thin_doubles(int dp) { return H * dp + H + OMAX * H + OMAX + 8 + 2; }
+__host__ __device__ constexpr int head_doubles(int dp, int nhid, int tab = TANH_TAB, int nw = 4) {
+    return ((thin_doubles(dp) + (nhid - 1) * 2 * H + 1) & ~1) + ((tab + 1) & ~1) + nw * 128;
 }
 
 // slot swizzle of the digit planes: 16-byte slot s of row r is stored at slot s ^ hs(r >> 2 & 3); with it the four
@@ -163,6 +166,14 @@ __host__ __device__ constexpr int stage_quota(int st, int np) {
                   st == 16 ? 25 : 26;
     const int v = (c * np + 25) / 26;                             // fewer products (LMIN = 5): same shape, scaled
     return st >= 17 ? np : (v > np ? np : v);
+}
+// the same for the 19 stages of the tanh(n / 512) epilogue (two vector instructions per element fewer: stage 7 is one
+// instruction, the e^2 + e^4 stage is gone); every product is out by stage 16, the last three stages are the digit permutes
+__host__ __device__ constexpr int stage_quota19(int st, int np) {
+    const int c = st < 2 ? 0 : st == 2 ? 3 : st == 3 ? 6 : st == 4 ? 8 : st == 5 ? 10 : st == 6 ? 11 : st == 7 ? 12 : st == 8 ? 13 :
+                  st == 9 ? 15 : st == 10 ? 18 : st == 11 ? 20 : st == 12 ? 22 : st == 13 ? 23 : st == 14 ? 24 : st == 15 ? 25 : 26;
+    const int v = (c * np + 25) / 26;
+    return st >= 16 ? np : (v > np ? np : v);
 }
 // is product k the first one of its level (then the accumulator input is the constant 0)
 __host__ __device__ constexpr bool prod_first(int lmin, int k) {

@@ -154,6 +154,11 @@ __device__ __forceinline__ double qn_tanh_f64_tab64(double x, const double* __re
     return __builtin_copysign(fma(fma(-T, T, 1.0), u, T), x);
 }
 
+// The same on a table of tanh(n / 512) (10241 values, 80 KB of LDS): two instructions fewer, for the kernel that has the LDS
+// (the 8-wave tanh form of qn_fused_i8.hip); function and error bound in qn_tanh512.h.
+#include "qn_tanh512.h"
+static __device__ const double qn_tanh_table512_g[QN_TANH_TAB512_N] = {QN_TANH_TAB512_VALUES};
+
 // relu with the reference's NaN semantics (torch.nn.ReLU: relu(NaN) = NaN, relu(x <= 0) = +0); `z > 0 ? z : 0` swallowed a NaN
 template <typename T> __device__ __forceinline__ T qn_relu(T z) { return z > T(0) ? z : (z != z ? z : T(0)); }
 // dz . act'(a) through the stored OUTPUT a = act(z), with the reference's semantics: tanh multiplies by 1 - a^2; relu is a
