@@ -1,14 +1,9 @@
-// Device HMC / MALA with a per-chain step size and a diagonal mass matrix, and their warm-up adaptation:
-//   qn_hmc_begin_s / qn_hmc_leap_s : the leapfrog kernels of qn_mcmc.hip (k_hmc_begin / k_hmc_leap) with eps a DEVICE array
-//                                    [C] and an optional per-parameter scale [C, p] (square root of the inverse mass)
-//   qn_hmc_adapt                   : one launch per warm-up step after the accept call: dual averaging of the step size
-//                                    (Hoffman & Gelman 2014, algorithm 5) and Welford moments of the state for the scale
-// The leapfrog runs in whitened momenta u = s * r (r the momentum, M^-1 = diag(s^2)): u ~ N(0, I), K = |u|^2 / 2, a kick is
-// u += (f eps_c) s * d logpost, a drift q += eps_c s * u -- the kernels of qn_mcmc.hip with the scalars half_kick / kick / eps
-// replaced by the per-element products (kick_c * s) and (eps_c * s).  Same grid, same element -> thread map, same Philox keys
-// and the same fixed-order partial sums, so with scale = 1 and equal eps_c the results are those kernels' bit for bit, and
-// qn_hmc_accept serves both.  HBM-bound elementwise work; all stores are ordinary vector stores, no atomics, no fences.
-#include "qn_hmc_step_s.h"      // k_hmc_begin_s / k_hmc_leap_s, shared with qn_temper.hip
+// The warm-up of device HMC / MALA with a per-chain step size and a diagonal mass matrix:
+//   qn_hmc_adapt : one launch per warm-up step after the accept call: dual averaging of the step size (Hoffman & Gelman 2014,
+//                  algorithm 5) and Welford moments of the state for the scale
+// It writes the arrays eps [C] and scale [C, p] that qn_hmc_begin_s / qn_hmc_leap_s read (qn_hmc_leap.hip, which states the
+// whitened leapfrog they run).  All stores are ordinary vector stores, no atomics, no fences.
+#include "qn_mcmc_shared.h"
 
 namespace {
 
@@ -83,35 +78,6 @@ __global__ __launch_bounds__(HBLK) void k_hmc_adapt(AdaptArgs a, const double* _
 }
 
 }  // namespace
-
-extern "C" int qn_hmc_begin_s(const double* cur, const double* grad_cur, double sigma, const double* eps,
-                              const double* scale, int C, int chain0, int64_t p, uint64_t seed, const int64_t* step_ptr,
-                              double* mom, double* q, double* kin_cur_parts, void* stream) {
-    if (!cur || !grad_cur || !eps || !step_ptr || !mom || !q || !kin_cur_parts || C <= 0 || C > 65535 || chain0 < 0 ||
-        p <= 0 || !(sigma > 0.0)) {
-        qn_set_error("qn_hmc_begin_s: bad argument");
-        return QN_EINVAL;
-    }
-    (void)hipGetLastError();
-    hmc_begin_s_launch(cur, grad_cur, sigma, eps, scale, nullptr, C, chain0, p, seed, step_ptr, mom, q, kin_cur_parts,
-                       static_cast<hipStream_t>(stream));
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
-
-extern "C" int qn_hmc_leap_s(const void* grad_q, int dtype, double sigma, const double* eps, const double* scale, int last,
-                             int C, int64_t p, double* mom, double* q, double* kin_prop_parts, void* stream) {
-    if (!grad_q || !eps || !mom || !q || (last && !kin_prop_parts) || C <= 0 || C > 65535 || p <= 0 || !(sigma > 0.0) ||
-        (dtype != QN_F64 && dtype != QN_F32)) {
-        qn_set_error("qn_hmc_leap_s: bad argument");
-        return QN_EINVAL;
-    }
-    (void)hipGetLastError();
-    hmc_leap_s_launch(grad_q, dtype, sigma, eps, scale, nullptr, last, C, p, mom, q, kin_prop_parts,
-                      static_cast<hipStream_t>(stream));
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
 
 extern "C" int qn_hmc_adapt(const double* cur, const double* alphas, int nmcmc, const int64_t* step_ptr, int parity, int C,
                             int64_t p, int m, double target_accept, int collect, int finish, int freeze, int n, double* da,

@@ -2,7 +2,8 @@
 //   qn_mcmc_propose : proposal = current + sqrt(diag) * z + c1 * z0      (Philox4x32-10 normals in-kernel)
 //                     or writes the standard normals z for a dense factor product
 //   qn_mcmc_accept  : log-posterior from the SSE, accept test, state / best / history / statistics update
-// Both read the step counter from DEVICE memory (the accept kernel increments it), so one step is a
+//   qn_hmc_accept   : the same accept kernel with the kinetic energies of the device HMC / MALA leapfrog (qn_hmc_leap.hip)
+// All read the step counter from DEVICE memory (the accept kernel increments it), so one step is a
 // static HIP graph: propose -> batched log-posterior -> accept.  HBM-bound elementwise work:
 // propose 3 x 8 B per element, accept <= 6 x 8 B per element.
 #include "qn_mcmc_shared.h"
@@ -486,81 +487,6 @@ __global__ __launch_bounds__(ABLK) void k_accept(AcceptArgs a, const double* __r
         if (b == 0) step_ptr[1 - a.par] = step + 1;
     }
 }
-
-
-// ---- Hamiltonian Monte Carlo on the device: geometry (HBLK, HUB, hmc_parts) and block_sum_256 are in qn_mcmc_shared.h
-// momentum z ~ N(0, I) (Philox stream 2*step, keyed by the global chain id), K_cur partials = sum z^2,
-// half kick with the cached gradient of the current state, first drift:
-//   mom = z + (eps/2) * gs * g_cur;   q = cur + eps * mom           (gs = -0.5 / sigma^2: d logpost = gs * d SSE)
-__global__ __launch_bounds__(HBLK) void k_hmc_begin(const double* __restrict__ cur, const double* __restrict__ gcur,
-                                                    double half_kick, double eps, int chain0, int64_t p, uint64_t seed,
-                                                    const int64_t* __restrict__ step_ptr, double* __restrict__ mom,
-                                                    double* __restrict__ q, double* __restrict__ kin_parts) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const uint64_t step = (uint64_t)*step_ptr;
-    const int64_t base = (int64_t)b * p;
-    const int64_t npair = (p + 1) / 2;
-    const int64_t pchunk = (npair + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * pchunk, hi = lo + pchunk < npair ? lo + pchunk : npair;
-    double ss = 0.0;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += HBLK) {
-        Philox ph;
-        ph.gen(seed, 2 * step, ctr_of(chain0 + b, 0, (uint64_t)j));
-        double za, zb;
-        normal2(ph, za, zb);
-        const int64_t e = 2 * j;
-        const double m0 = fma(half_kick, gcur[base + e], za);
-        mom[base + e] = m0;
-        q[base + e] = fma(eps, m0, cur[base + e]);
-        ss = fma(za, za, ss);
-        if (e + 1 < p) {
-            const double m1 = fma(half_kick, gcur[base + e + 1], zb);
-            mom[base + e + 1] = m1;
-            q[base + e + 1] = fma(eps, m1, cur[base + e + 1]);
-            ss = fma(zb, zb, ss);
-        }
-    }
-    const double tot = block_sum_256(ss, red);
-    if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
-}
-// kick with the gradient at q, then (inner step) drift, or (last step) the proposal's kinetic energy partials:
-//   mom += kick * g;   last ? K_prop partial = sum mom^2 : q += eps * mom
-template <typename TG>
-__global__ __launch_bounds__(HBLK) void k_hmc_leap(const TG* __restrict__ g, double kick, double eps, int last, int64_t p,
-                                                   double* __restrict__ mom, double* __restrict__ q,
-                                                   double* __restrict__ kin_parts) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * p;
-    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
-    double ss = 0.0;
-    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
-        double gv[HUB], mv[HUB], qv[HUB];
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            const bool in = e < hi;
-            gv[u] = in ? (double)g[base + e] : 0.0;
-            mv[u] = in ? mom[base + e] : 0.0;
-            qv[u] = (in && !last) ? q[base + e] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            if (e >= hi) break;
-            const double m = fma(kick, gv[u], mv[u]);
-            mom[base + e] = m;
-            if (last) ss = fma(m, m, ss);
-            else q[base + e] = fma(eps, m, qv[u]);
-        }
-    }
-    if (last) {
-        const double tot = block_sum_256(ss, red);
-        if (threadIdx.x == 0) kin_parts[(int64_t)b * gridDim.x + blockIdx.x] = tot;
-    }
-}
 }  // namespace
 
 extern "C" int qn_mcmc_propose(const double* cur, const double* sd, double c1, int C, int chain0, int64_t p,
@@ -702,45 +628,8 @@ extern "C" int qn_mcmc_accept_propose(const double* prop, const double* sse_prop
                          kcur, sumx, step_ptr, parity, stream);
 }
 
-// ---------------------------------------------------------------------------------------------- HMC entry points
+// ------------------------------------------------------ HMC accept entry points (the leapfrog calls: qn_hmc_leap.hip)
 extern "C" int qn_hmc_parts(int64_t p) { return p > 0 ? hmc_parts(p) : QN_EINVAL; }
-
-extern "C" int qn_hmc_begin(const double* cur, const double* grad_cur, double sigma, double epsilon, int C, int chain0,
-                            int64_t p, uint64_t seed, const int64_t* step_ptr, double* mom, double* q, double* kin_cur_parts,
-                            void* stream) {
-    if (!cur || !grad_cur || !step_ptr || !mom || !q || !kin_cur_parts || C <= 0 || C > 65535 || chain0 < 0 || p <= 0 ||
-        !(sigma > 0.0)) {
-        qn_set_error("qn_hmc_begin: bad argument");
-        return QN_EINVAL;
-    }
-    const double gs = -0.5 / (sigma * sigma);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_hmc_begin, dim3(hmc_parts(p), C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), cur, grad_cur,
-                       0.5 * epsilon * gs, epsilon, chain0, p, seed, step_ptr, mom, q, kin_cur_parts);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
-
-extern "C" int qn_hmc_leap(const void* grad_q, int dtype, double sigma, double epsilon, int last, int C, int64_t p, double* mom,
-                           double* q, double* kin_prop_parts, void* stream) {
-    if (!grad_q || !mom || !q || (last && !kin_prop_parts) || C <= 0 || C > 65535 || p <= 0 || !(sigma > 0.0) ||
-        (dtype != QN_F64 && dtype != QN_F32)) {
-        qn_set_error("qn_hmc_leap: bad argument");
-        return QN_EINVAL;
-    }
-    const double gs = -0.5 / (sigma * sigma);
-    const double kick = (last ? 0.5 : 1.0) * epsilon * gs;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (dtype == QN_F32)
-        hipLaunchKernelGGL(k_hmc_leap<float>, dim3(hmc_parts(p), C), dim3(HBLK), 0, st, (const float*)grad_q, kick, epsilon,
-                           last ? 1 : 0, p, mom, q, kin_prop_parts);
-    else
-        hipLaunchKernelGGL(k_hmc_leap<double>, dim3(hmc_parts(p), C), dim3(HBLK), 0, st, (const double*)grad_q, kick, epsilon,
-                           last ? 1 : 0, p, mom, q, kin_prop_parts);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
 
 static int hmc_accept_any(const char* who, const double* beta, const double* q, const double* grad_q, const double* sse_q,
                           const double* kin_cur_parts, const double* kin_prop_parts, double sigma, int n_rows, int C, int chain0,

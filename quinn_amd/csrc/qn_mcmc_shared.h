@@ -1,4 +1,4 @@
-// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_adapt.hip): the Philox4x32-10 generator and
+// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_leap.hip, qn_hmc_adapt.hip, qn_temper.hip, qn_sgmcmc.hip, qn_prior.hip): the Philox4x32-10 generator and
 // its counter layout, the normal / uniform transforms, the 8-byte aligned pair accesses and the geometry + fixed-order block
 // sum of the HMC elementwise kernels.  Everything is internal linkage: each translation unit gets its own copy.
 #pragma once
@@ -79,7 +79,7 @@ __device__ __forceinline__ double block_sum_256(double v, double* red) {
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
-inline int hmc_parts(int64_t p) {                      // workgroups per chain: a function of p alone (see k_hmc_begin)
+inline int hmc_parts(int64_t p) {                      // workgroups per chain: a function of p alone (see k_hmc_begin, qn_hmc_leap.hip)
     const int64_t n = (p + HBLK * HUB - 1) / (HBLK * HUB);
     return n > 64 ? 64 : (n < 1 ? 1 : (int)n);
 }

@@ -6,7 +6,7 @@
 //     g'   = g + (2 lam) w               ->  gs g'   = gs g - w / priorsigma^2
 // and one qn_prior_fold launch behind a forward / gradient call hands every accept, leapfrog, adapt, swap and SG kernel the
 // posterior with the prior, their code untouched.
-// Gradient: elementwise, the element -> thread map of k_hmc_leap_s; every entry is formed in float64 with one rounding per
+// Gradient: elementwise, the element -> thread map of k_hmc_leap; every entry is formed in float64 with one rounding per
 // operation (FP contraction is off for the whole file: hipcc would fuse the product into the sum), a float32 gradient is
 // widened, updated and rounded once.  Sum of squares: workgroup 0 of every chain sums the WHOLE row itself (a strided loop of
 // its 256 threads, four accumulators per thread, block_sum_256), so the order of the additions depends on p alone -- not on the

@@ -1,8 +1,7 @@
 // Replica exchange (parallel tempering) for the device HMC / MALA engines:
-//   qn_hmc_begin_t / qn_hmc_leap_t : qn_hmc_begin_s / qn_hmc_leap_s with a per-chain inverse temperature beta [C]: chain c
-//                                    samples pi^beta_c, the force is beta_c * d logpost (kernels: qn_hmc_step_s.h)
-//   qn_hmc_accept_t                : qn_hmc_accept with beta_c in the MH ratio (qn_mcmc.hip, next to the kernel it shares)
-//   qn_pt_swap                     : one exchange round between neighbouring rungs of every ladder
+//   qn_pt_swap : one exchange round between neighbouring rungs of every ladder
+// The tempered step itself is elsewhere: qn_hmc_begin_t / qn_hmc_leap_t, the leapfrog with the force beta_c * d logpost, in
+// qn_hmc_leap.hip; qn_hmc_accept_t, qn_hmc_accept with beta_c in the MH ratio, in qn_mcmc.hip next to the kernel it shares.
 // Chains are ladder-major: chain c is rung c % R of ladder c / R, 1 = beta_0 > ... > beta_{R-1}.  Round `round` pairs
 // (c, c + 1) for c % R in {e, e + 2, ...}, e = round & 1 (deterministic even-odd scheme); the pair exchanges its states with
 // probability min(1, exp((beta_c - beta_{c+1}) (lp_{c+1} - lp_c))), lp the UNTEMPERED log-posteriors.
@@ -11,7 +10,7 @@
 // are issued before the decision is known, and workgroup 0 of every chain writes slot 1 - par (of rid: slot 1 - rpar; the accept
 // kernel does not know rid, so only exchange rounds flip its parity).  Plain vector loads and stores,
 // no atomics, no fences.
-#include "qn_hmc_step_s.h"
+#include "qn_mcmc_shared.h"
 
 namespace {
 
@@ -116,36 +115,6 @@ int swap_parts(int64_t p) {
 }
 
 }  // namespace
-
-extern "C" int qn_hmc_begin_t(const double* cur, const double* grad_cur, double sigma, const double* eps, const double* scale,
-                              const double* beta, int C, int chain0, int64_t p, uint64_t seed, const int64_t* step_ptr,
-                              double* mom, double* q, double* kin_cur_parts, void* stream) {
-    if (!cur || !grad_cur || !eps || !step_ptr || !mom || !q || !kin_cur_parts || C <= 0 || C > 65535 || chain0 < 0 ||
-        p <= 0 || !(sigma > 0.0)) {
-        qn_set_error("qn_hmc_begin_t: bad argument");
-        return QN_EINVAL;
-    }
-    (void)hipGetLastError();
-    hmc_begin_s_launch(cur, grad_cur, sigma, eps, scale, beta, C, chain0, p, seed, step_ptr, mom, q, kin_cur_parts,
-                       static_cast<hipStream_t>(stream));
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
-
-extern "C" int qn_hmc_leap_t(const void* grad_q, int dtype, double sigma, const double* eps, const double* scale,
-                             const double* beta, int last, int C, int64_t p, double* mom, double* q, double* kin_prop_parts,
-                             void* stream) {
-    if (!grad_q || !eps || !mom || !q || (last && !kin_prop_parts) || C <= 0 || C > 65535 || p <= 0 || !(sigma > 0.0) ||
-        (dtype != QN_F64 && dtype != QN_F32)) {
-        qn_set_error("qn_hmc_leap_t: bad argument");
-        return QN_EINVAL;
-    }
-    (void)hipGetLastError();
-    hmc_leap_s_launch(grad_q, dtype, sigma, eps, scale, beta, last, C, p, mom, q, kin_prop_parts,
-                      static_cast<hipStream_t>(stream));
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
 
 extern "C" int qn_pt_swap(double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* chain,
                           const double* beta, int32_t* rid, int32_t* rep, int64_t* swap_acc, int64_t* swap_try,

@@ -1,7 +1,7 @@
 """Warm-up adaptation of HMC / MALA: per-chain step size by dual averaging, per-chain diagonal mass by windowed Welford moments.
 
 One contract for the host samplers (`HMC`, `MALA`; numpy, this file) and the device engines (`DeviceHMC`, `DeviceMALA`;
-qn_hmc_adapt, csrc/qn_hmc_adapt.hip).  Chain c carries a step size eps_c and a positive per-parameter scale s[c, :] (square
+the _s leapfrog of csrc/qn_hmc_leap.hip, qn_hmc_adapt of csrc/qn_hmc_adapt.hip).  Chain c carries a step size eps_c and a positive per-parameter scale s[c, :] (square
 root of the inverse mass, 1 at the start); the leapfrog runs in whitened momenta u = s * r:
 
     z ~ N(0, I);  u = z + (eps_c/2) s*g(cur);  q = cur + eps_c s*u

@@ -15,7 +15,8 @@ state is the accepted proposal's, the proposal's log-posterior comes with its gr
 of steps (parity 0, 1) are captured once in a HIP graph and replayed.  Random streams are keyed by (seed, step, global
 chain id): a chain's path does not depend on how the chains are split over ranks or launches (only the summation order
 of its SSE does, through the row split the gradient kernel picks for the batch size).  Chains agree with the host `HMC`
-in distribution, not bit for bit (Philox instead of numpy's MT19937).
+in distribution, not bit for bit (Philox instead of numpy's MT19937).  Every begin / leap entry point named here and below
+is an instantiation of the one kernel pair of csrc/qn_hmc_leap.hip; the accept calls are in csrc/qn_mcmc.hip.
 
 `adapt` > 0 warm-up steps tune a per-chain step size and, with `adapt_mass`, a per-chain diagonal mass matrix on the device
 (`quinn_amd.mcmc.adapt` states the contract): every step then runs qn_hmc_begin_s / qn_hmc_leap_s, which read the step
@@ -47,6 +48,10 @@ from .tempering import check_temper_args, check_whole_ladders
 from .device_engine import DeviceEngine
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
@@ -69,31 +74,53 @@ class DeviceHMC(DeviceEngine):
         self._ladder = None if ladder is None else check_temper_args(ladder, beta_min, swap_every, chain0=self.chain0,
                                                                      use_graph=self.use_graph)
 
+    def _begin(self, s, st):
+        """Enqueue the begin call of a step.  The entry point follows from what the state holds: s['beta'] (a ladder) -> _t,
+        else s['eps'] (a device step size: warm-up) -> _s, else the fixed step `epsilon`; scale: s['scale'] or None (1)."""
+        C, p = s['cur'].shape
+        eps, scale, beta = _ptr(s.get('eps')), _ptr(s.get('scale')), _ptr(s.get('beta'))
+        cur, grad_cur, sigma = s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma
+        rest = (C, self.chain0, p, self.seed, self._step_ptr(s), s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st)
+        if beta is not None:
+            _lib.check(self._L.qn_hmc_begin_t(cur, grad_cur, sigma, eps, scale, beta, *rest), "qn_hmc_begin_t")
+        elif eps is not None:
+            _lib.check(self._L.qn_hmc_begin_s(cur, grad_cur, sigma, eps, scale, *rest), "qn_hmc_begin_s")
+        else:
+            _lib.check(self._L.qn_hmc_begin(cur, grad_cur, sigma, self.epsilon, *rest), "qn_hmc_begin")
+
+    def _leap(self, s, last, st):
+        """Enqueue the leap call behind a gradient at s['q']; the entry point is chosen as in `_begin`."""
+        C, p = s['cur'].shape
+        eps, scale, beta = _ptr(s.get('eps')), _ptr(s.get('scale')), _ptr(s.get('beta'))
+        grad_q, dtype, sigma = s['gq'].data_ptr(), self.op.qdt, self.sigma
+        rest = (int(last), C, p, s['mom'].data_ptr(), s['q'].data_ptr(), s['kprop'].data_ptr(), st)
+        if beta is not None:
+            _lib.check(self._L.qn_hmc_leap_t(grad_q, dtype, sigma, eps, scale, beta, *rest), "qn_hmc_leap_t")
+        elif eps is not None:
+            _lib.check(self._L.qn_hmc_leap_s(grad_q, dtype, sigma, eps, scale, *rest), "qn_hmc_leap_s")
+        else:
+            _lib.check(self._L.qn_hmc_leap(grad_q, dtype, sigma, self.epsilon, *rest), "qn_hmc_leap")
+
     def _step(self, s, nmcmc):
-        """Enqueue one HMC step on the current stream (reads slot s['par'] of the scalars, writes the other).  s['kern']: the
-        begin / leap entry points of this run and their step-size arguments -- (epsilon), or with warm-up the device arrays
-        (eps [C], scale [C, p] or None: 1)."""
+        """Enqueue one HMC step on the current stream (reads slot s['par'] of the scalars, writes the other)."""
         st = self._stream()
         C, p = s['cur'].shape
-        begin, begin_name, leap, leap_name, eps = s['kern']
-        accept, accept_name, accept_extra = s.get('accept') or (self._L.qn_hmc_accept, "qn_hmc_accept", ())
-        _lib.check(begin(s['cur'].data_ptr(), s['gcur'].data_ptr(), self.sigma, *eps, C, self.chain0, p, self.seed,
-                         self._step_ptr(s), s['mom'].data_ptr(), s['q'].data_ptr(), s['kcur'].data_ptr(), st), begin_name)
+        self._begin(s, st)
         for j in range(self.L):
-            last = j == self.L - 1
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
             if self._prior is not None:                                       # (the float64 positions, also under a float32 operator)
                 self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
-            _lib.check(leap(s['gq'].data_ptr(), self.op.qdt, self.sigma, *eps, int(last), C, p, s['mom'].data_ptr(),
-                            s['q'].data_ptr(), s['kprop'].data_ptr(), st), leap_name)
+            self._leap(s, j == self.L - 1, st)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
-        _lib.check(accept(
-            s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
-            self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
-            s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(),
-            s['chain'].data_ptr() if s['chain'] is not None else None, s['lps'].data_ptr(), s['alphas'].data_ptr(),
-            s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'], *accept_extra, st), accept_name)
+        args = (s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
+                self.sigma, self.op.N, C, self.chain0, p, nmcmc, self.seed, s['cur'].data_ptr(), s['gcur'].data_ptr(),
+                s['cur_lp'].data_ptr(), s['best'].data_ptr(), s['best_lp'].data_ptr(), _ptr(s['chain']), s['lps'].data_ptr(),
+                s['alphas'].data_ptr(), s['nacc'].data_ptr(), s['step'].data_ptr(), s['par'])
+        if s.get('beta') is not None:
+            _lib.check(self._L.qn_hmc_accept_t(*args, s['beta'].data_ptr(), st), "qn_hmc_accept_t")
+        else:
+            _lib.check(self._L.qn_hmc_accept(*args, st), "qn_hmc_accept")
         s['par'] ^= 1
 
     def _swap_step(self, s, nmcmc):
@@ -114,11 +141,10 @@ class DeviceHMC(DeviceEngine):
         """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
         from the slot of the step counter the accept call wrote, which is s['par'] after `_step`."""
         C, p = s['cur'].shape
-        ptr = lambda t: None if t is None else t.data_ptr()
         _lib.check(self._L.qn_hmc_adapt(s['cur'].data_ptr(), s['alphas'].data_ptr(), nmcmc, s['step'].data_ptr(), s['par'], C, p,
                                         a['m'], self.target_accept, int(a['collect']), int(a['finish']), int(a['freeze']),
-                                        a['n'], s['da'].data_ptr(), s['eps'].data_ptr(), ptr(s['wmean']), ptr(s['wm2']),
-                                        ptr(s['scale']), self._stream()), "qn_hmc_adapt")
+                                        a['n'], s['da'].data_ptr(), s['eps'].data_ptr(), _ptr(s['wmean']), _ptr(s['wm2']),
+                                        _ptr(s['scale']), self._stream()), "qn_hmc_adapt")
 
     def _ngroups(self, C):
         if self.groups is None:
@@ -164,8 +190,7 @@ class DeviceHMC(DeviceEngine):
                   'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
                   'qc': torch.empty(C, p, dtype=self.op.tdt, device=dev) if f32op else None,
                   'g64': torch.empty(C, p, dtype=f64, device=dev) if f32op else None,
-                  'kcur': torch.empty(C, nk, dtype=f64, device=dev), 'kprop': torch.empty(C, nk, dtype=f64, device=dev),
-                  'kern': (self._L.qn_hmc_begin, "qn_hmc_begin", self._L.qn_hmc_leap, "qn_hmc_leap", (self.epsilon,))})
+                  'kcur': torch.empty(C, nk, dtype=f64, device=dev), 'kprop': torch.empty(C, nk, dtype=f64, device=dev)})
         i = 0
         step = self._step
         eps0 = self.epsilon
@@ -182,9 +207,6 @@ class DeviceHMC(DeviceEngine):
             s['round'] = 0
             eps0 = self.epsilon / torch.sqrt(s['beta'])
             s['eps'] = eps0.clone()
-            s['kern'] = (self._L.qn_hmc_begin_t, "qn_hmc_begin_t", self._L.qn_hmc_leap_t, "qn_hmc_leap_t",
-                         (s['eps'].data_ptr(), None, s['beta'].data_ptr()))
-            s['accept'] = (self._L.qn_hmc_accept_t, "qn_hmc_accept_t", (s['beta'].data_ptr(),))
             plain = self._step
 
             def step(s, nmcmc, a=None):
@@ -207,12 +229,6 @@ class DeviceHMC(DeviceEngine):
             s['scale'] = torch.ones(C, p, dtype=f64, device=dev) if mass else None
             s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
-            scale_ptr = None if s['scale'] is None else s['scale'].data_ptr()
-            if self._ladder is None:
-                s['kern'] = (self._L.qn_hmc_begin_s, "qn_hmc_begin_s", self._L.qn_hmc_leap_s, "qn_hmc_leap_s",
-                             (s['eps'].data_ptr(), scale_ptr))
-            else:
-                s['kern'] = s['kern'][:4] + ((s['eps'].data_ptr(), scale_ptr, s['beta'].data_ptr()),)
             for a in plan:
                 if self._ladder is None:
                     step(s, nmcmc)

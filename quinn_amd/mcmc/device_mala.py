@@ -4,7 +4,8 @@ The reference's `MALA.sampler` (quinn/mcmc/mala.py:24-53) draws p ~ N(0, I), pro
     x' = x + (eps^2 / 2) grad(x) + eps p,       p' = p + eps (grad(x) + grad(x')) / 2,
 and hands K = |p|^2 / 2, K' = |p'|^2 / 2 to the MH test of `MCMCBase.run` (mcmc.py:65-85) -- which is, term for term, one
 leapfrog step: half kick p + (eps / 2) grad(x), drift x + eps (that), half kick with grad(x') (the reference's own note:
-"MALA is actually exactly HMC with L = 1").  So the device engine IS the device HMC engine with one leapfrog step:
+"MALA is actually exactly HMC with L = 1").  So the device engine IS the device HMC engine with one leapfrog step
+(kernels: csrc/qn_hmc_leap.hip, accept: csrc/qn_mcmc.hip):
 
     qn_hmc_begin   momenta (in-kernel Philox keyed by the GLOBAL chain id), K partials, half kick with the cached gradient
                    of the current state, drift  ->  the Langevin proposal

@@ -1,5 +1,5 @@
 """Replica exchange (parallel tempering; Swendsen & Wang 1986, Geyer 1991) for the device HMC / MALA engines: the contract of
-qn_hmc_begin_t / qn_hmc_leap_t / qn_hmc_accept_t / qn_pt_swap (csrc/qn_temper.hip, include/quinn_amd.h), restated in numpy.
+qn_hmc_begin_t / qn_hmc_leap_t / qn_hmc_accept_t / qn_pt_swap (csrc/qn_hmc_leap.hip, qn_mcmc.hip, qn_temper.hip; include/quinn_amd.h), restated in numpy.
 
 The C lock-step chains are K = C / R ladders of R rungs, ladder-major: chain c is rung c % R of ladder c // R and samples
 pi(w)^beta_r with 1 = beta_0 > ... > beta_{R-1} > 0.  A rung's HMC step is the untempered one with the force beta_r * d logpost and

@@ -1,4 +1,4 @@
-"""GPU: device HMC / MALA warm-up (csrc/qn_hmc_adapt.hip).  qn_hmc_begin_s / qn_hmc_leap_s against the fixed-step kernels bit
+"""GPU: device HMC / MALA warm-up (csrc/qn_hmc_leap.hip, csrc/qn_hmc_adapt.hip).  qn_hmc_begin_s / qn_hmc_leap_s against the fixed-step kernels bit
 for bit (scale NULL / 1, equal step sizes) and against the numpy whitened leapfrog (different step sizes, random scale);
 qn_hmc_adapt against the numpy recurrences of quinn_amd/mcmc/adapt.py; the engine on a Gaussian posterior from a step size
 at which the unadapted engine accepts nothing; independence from the chain split, graph replay, and the solver."""
@@ -30,10 +30,10 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _one_step(kind, cur, gcur, grads, sigma, eps, scale, chain0, seed, step, f32=False):
+def _one_step(kind, cur, gcur, grads, sigma, eps, scale, chain0, seed, step, f32=False, beta=None):
     """One leapfrog trajectory through the C ABI with the given gradient arrays (one per leapfrog step) -> mom, q, K_cur
     partials, K_prop partials (host).  kind 'fixed': qn_hmc_begin / qn_hmc_leap with the scalar eps; 's': the _s calls with
-    eps [C] and scale [C, p] or None on the device."""
+    eps [C] and scale [C, p] or None on the device; 't': the _t calls with those and beta [C] or None."""
     L = _lib.lib()
     C, p = cur.shape
     nk = L.qn_hmc_parts(p)
@@ -44,6 +44,9 @@ def _one_step(kind, cur, gcur, grads, sigma, eps, scale, chain0, seed, step, f32
     if kind == 'fixed':
         _lib.check(L.qn_hmc_begin(cur.data_ptr(), gcur.data_ptr(), sigma, eps, C, chain0, p, seed, st.data_ptr(),
                                   mom.data_ptr(), q.data_ptr(), kc.data_ptr(), None), "qn_hmc_begin")
+    elif kind == 't':
+        _lib.check(L.qn_hmc_begin_t(cur.data_ptr(), gcur.data_ptr(), sigma, eps.data_ptr(), _ptr(scale), _ptr(beta), C, chain0,
+                                    p, seed, st.data_ptr(), mom.data_ptr(), q.data_ptr(), kc.data_ptr(), None), "qn_hmc_begin_t")
     else:
         _lib.check(L.qn_hmc_begin_s(cur.data_ptr(), gcur.data_ptr(), sigma, eps.data_ptr(), _ptr(scale), C, chain0, p, seed,
                                     st.data_ptr(), mom.data_ptr(), q.data_ptr(), kc.data_ptr(), None), "qn_hmc_begin_s")
@@ -54,6 +57,9 @@ def _one_step(kind, cur, gcur, grads, sigma, eps, scale, chain0, seed, step, f32
         if kind == 'fixed':
             _lib.check(L.qn_hmc_leap(g.data_ptr(), dt, sigma, eps, last, C, p, mom.data_ptr(), q.data_ptr(), kp.data_ptr(),
                                      None), "qn_hmc_leap")
+        elif kind == 't':
+            _lib.check(L.qn_hmc_leap_t(g.data_ptr(), dt, sigma, eps.data_ptr(), _ptr(scale), _ptr(beta), last, C, p,
+                                       mom.data_ptr(), q.data_ptr(), kp.data_ptr(), None), "qn_hmc_leap_t")
         else:
             _lib.check(L.qn_hmc_leap_s(g.data_ptr(), dt, sigma, eps.data_ptr(), _ptr(scale), last, C, p, mom.data_ptr(),
                                        q.data_ptr(), kp.data_ptr(), None), "qn_hmc_leap_s")
@@ -81,6 +87,32 @@ def test_scaled_kernels_equal_the_fixed_step_kernels_bit_for_bit(dims, L_):
             for name, a, b in zip(("mom", "q", "kin_cur", "kin_prop"), got, ref):
                 assert np.array_equal(a, b), (name, f32, scale is None)
     assert np.all(ref[2] > 0) and np.all(ref[3] > 0)
+
+
+@pytest.mark.parametrize("dims", [(1, 8, 8, 1), (1, 64, 64, 1)])
+@pytest.mark.parametrize("L_", [1, 3])
+def test_tempered_kernels_without_a_temperature_equal_both_others_bit_for_bit(dims, L_):
+    """p = 97 (odd tail, one workgroup per chain) and 4353 (five workgroups), C = 3: qn_hmc_begin_t / qn_hmc_leap_t with beta
+    NULL and beta = 1, each with scale NULL and scale = 1, give the momenta, positions and both kinetic partial sums of the
+    fixed-step and of the _s calls, float64 and float32 gradients: all three are one kernel."""
+    p = MLPArch(dims, "tanh").nparams
+    assert p == {(1, 8, 8, 1): 97, (1, 64, 64, 1): 4353}[dims]
+    assert _lib.lib().qn_hmc_parts(p) == (5 if p == 4353 else 1)
+    rs = np.random.RandomState(p + L_)
+    C, sigma, eps, seed = 3, 0.2, 0.0123, 991
+    cur, gcur = _dev(0.3 * rs.randn(C, p)), _dev(5 * rs.randn(C, p))
+    grads = [_dev(5 * rs.randn(C, p)) for _ in range(L_)]
+    epsv = torch.full((C,), eps, dtype=F64, device="cuda")
+    ones = torch.ones(C, p, dtype=F64, device="cuda")
+    for f32 in (False, True):
+        fixed = _one_step('fixed', cur, gcur, grads, sigma, eps, None, 4, seed, 6, f32)
+        for scale in (None, ones):
+            s = _one_step('s', cur, gcur, grads, sigma, epsv, scale, 4, seed, 6, f32)
+            for beta in (None, torch.ones(C, dtype=F64, device="cuda")):
+                got = _one_step('t', cur, gcur, grads, sigma, epsv, scale, 4, seed, 6, f32, beta=beta)
+                for name, a, b, c in zip(("mom", "q", "kin_cur", "kin_prop"), got, fixed, s):
+                    assert np.array_equal(a, b) and np.array_equal(a, c), (name, f32, scale is None, beta is None)
+    assert np.all(fixed[2] > 0) and np.all(fixed[3] > 0)
 
 
 def _close(got, ref, rtol):

@@ -1,4 +1,4 @@
-"""GPU: replica exchange for the device HMC / MALA engines (csrc/qn_temper.hip, quinn_amd/mcmc/tempering.py).  The tempered
+"""GPU: replica exchange for the device HMC / MALA engines (csrc/qn_hmc_leap.hip, csrc/qn_temper.hip, quinn_amd/mcmc/tempering.py).  The tempered
 entry points with beta = 1 against the untempered engines bit for bit; qn_pt_swap against `tempering.swap_round`; exactness of
 every rung on a Gaussian target; a bimodal posterior whose second mode only a ladder reaches; the solver."""
 import os
