@@ -5,7 +5,13 @@ an exception is raised.
 """
 import ctypes
 import os
+import re
 import subprocess
+
+# torch ships its own HIP runtime (torch/lib/libamdhip64.so, same SONAME as /opt/rocm's).
+# It must be the one already mapped when this library is loaded, otherwise the process ends
+# up with two runtimes and ours sees no device / cannot share torch's streams and memory.
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -15,25 +21,73 @@ SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "q
 # sources that #include another source (the second object of a file compiled in two parts): rebuilt when that one changes
 SOURCE_DEPS = {"qn_wide_u_i8.hip": ["qn_wide_i8.hip"], "qn_fused_d8.hip": ["qn_fused.hip"], "qn_fused_o16.hip": ["qn_fused.hip"]}
 
-QN_F64, QN_F32 = 0, 1
-ACT_CODES = {"identity": 0, "tanh": 1, "relu": 2}
-PATH_AUTO, PATH_GENERIC, PATH_FUSED, PATH_FUSED_DP = 0, 1, 2, 3
-ARITH_PLAIN, ARITH_I8_FUSED, ARITH_I8_WIDE, ARITH_I8_LAYERS = 0, 1, 2, 3
-CURV_HESS_FULL, CURV_EF_DIAG, CURV_GGN_FULL, CURV_GGN_DIAG = 0, 1, 2, 3
-GLM_COV_FULL, GLM_COV_DIAG = 0, 1
-SWAG_INIT, SWAG_SGD, SWAG_SGD_COLLECT = 0, 1, 2
-SCORE_LPPD, SCORE_PWAIC, SCORE_PIT, SCORE_CRPS, SCORE_MOMENTS, SCORE_NOUT = 1, 2, 4, 8, 16, 6
-
-# every symbol include/quinn_amd.h declares (tests check the .so exports all of them)
-SYMBOLS = ["qn_mlp_desc_create", "qn_rnet_desc_create", "qn_rnet_desc_set_uses", "qn_mlp_desc_destroy", "qn_mlp_num_params", "qn_workspace_bytes",
-           "qn_mlp_path", "qn_mlp_arith", "qn_mlp_desc_set_path", "qn_mlp_desc_set_plan_batch", "qn_mlp_sse_fwd", "qn_mlp_sse_parts", "qn_mlp_sse_fwd_parts", "qn_mlp_sse_fwdbwd", "qn_vi_sample_kl",
-           "qn_vi_grad", "qn_adam_batched", "qn_mcmc_propose", "qn_mcmc_propose_hist", "qn_mcmc_hist_block_steps", "qn_mcmc_hist_block_coef_bytes", "qn_mcmc_propose_hist_block",
-           "qn_mcmc_apply_delta", "qn_mcmc_accept", "qn_mcmc_accept_propose", "qn_hmc_parts", "qn_hmc_begin", "qn_hmc_leap", "qn_hmc_accept", "qn_hmc_begin_s", "qn_hmc_leap_s", "qn_hmc_adapt", "qn_hmc_begin_t", "qn_hmc_leap_t", "qn_hmc_accept_t", "qn_pt_swap", "qn_sg_rows", "qn_sg_step", "qn_prior_fold", "qn_pred_moments", "qn_curv_workspace_bytes", "qn_mlp_curv", "qn_glm_workspace_bytes", "qn_mlp_glm_predict", "qn_sobolev_workspace_bytes", "qn_mlp_input_jac", "qn_mlp_sobolev_fwdbwd", "qn_swag_step", "qn_swag_sample", "qn_kron_layout", "qn_kron_workspace_bytes", "qn_mlp_kron_factors", "qn_kron_glm_workspace_bytes", "qn_mlp_kron_glm_predict", "qn_kron_sample", "qn_chain_stats_workspace_bytes", "qn_chain_stats", "qn_pred_score_workspace_bytes", "qn_pred_score", "qn_debug_tanh", "qn_debug_tanh_finite", "qn_debug_tanh_table", "qn_last_error",
-           "qn_version"]
+HEADER = os.path.join(_HERE, "..", "include", "quinn_amd.h")       # the one place a signature or a code is written
 
 
 class QuinnAmdError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_INT = r"(-?(?:0[xX][0-9a-fA-F]+|\d+))"
+
+
+def _ctype(decl, ret, where):
+    """The ctypes type of the C type `decl` (`where`: function and text, for the message).  Every pointer parameter is a
+    c_void_p -- it takes None, an address, a ctypes array or byref() -- and a returned `const char*` a c_char_p."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if ret and words == ["void"]:
+        return None
+    if ret and words == ["char", "*"]:
+        return ctypes.c_char_p
+    if not ret and "*" in words:
+        return ctypes.c_void_p
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise QuinnAmdError(f"{where}: unknown type '{decl.strip()}'")
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """(functions, constants) of the text of a C header.  functions: name -> (restype, [argtypes]) of every qn_* prototype, in
+    the order of declaration; constants: name -> value of every `#define QN_X <integer>` and `enum { QN_X = <integer>, ... }`
+    member.  Strict: a type that is neither in _SCALARS nor a pointer, a parameter without a name, or a `qn_name(` in a
+    declaration of any other shape raises QuinnAmdError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(QN_\w+)[ \t]+" + _INT + r"[ \t]*$", text, re.M)}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        constants.update((k, int(v, 0)) for k, v in re.findall(r"\b(QN_\w+)\s*=\s*" + _INT + r"\s*(?:,|$)", body))
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    functions = {}
+
+    def prototype(m):
+        ret, name, params = m.group(1), m.group(2), " ".join(m.group(3).split())
+        argtypes = []
+        for par in ([] if params == "void" else [par.strip() for par in params.split(",")]):
+            split = re.fullmatch(r"(\S.*?)\s*\b(\w+)", par)
+            if not split:
+                raise QuinnAmdError(f"{name}({params}): no type and name in '{par}'")
+            argtypes.append(_ctype(split.group(1), False, f"{name}({params}), parameter '{par}'"))
+        functions[name] = (_ctype(ret, True, f"{name}, return"), argtypes)
+        return " "
+
+    rest = re.sub(r"([A-Za-z_][\w\s*]*?)\b(qn_\w+)\s*\(([^()]*)\)\s*;", prototype, text)
+    left = re.search(r"\b(qn_\w+)\s*\(", rest)
+    if left:
+        raise QuinnAmdError(f"{left.group(1)}: not a plain prototype: '{' '.join(rest[left.start():].split(';')[0].split())}'")
+    return functions, constants
+
+
+with open(HEADER) as _f:
+    FUNCTIONS, CONSTANTS = parse_header(_f.read())
+SYMBOLS = list(FUNCTIONS)         # every symbol include/quinn_amd.h declares (tests check the .so exports all of them)
+QN_F64, QN_F32 = CONSTANTS["QN_F64"], CONSTANTS["QN_F32"]
+# keyed by the reference's activation names (quinn/nns/mlp.py:46-84)
+ACT_CODES = {"identity": CONSTANTS["QN_ACT_IDENTITY"], "tanh": CONSTANTS["QN_ACT_TANH"], "relu": CONSTANTS["QN_ACT_RELU"]}
+# PATH_AUTO .., ARITH_PLAIN .., CURV_HESS_FULL .., GLM_COV_FULL .., SWAG_INIT .., SCORE_LPPD .. SCORE_NOUT: the header's
+# codes of these families under their names without the QN_ prefix
+globals().update((k[3:], v) for k, v in CONSTANTS.items()
+                 if k.startswith(("QN_PATH_", "QN_ARITH_", "QN_CURV_", "QN_GLM_", "QN_SWAG_", "QN_SCORE_")))
 
 
 def build(force=False, verbose=False, jobs=None):
@@ -48,7 +102,7 @@ def build(force=False, verbose=False, jobs=None):
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
-           [os.path.join(_HERE, "..", "include", "quinn_amd.h")]
+           [HEADER]
     hnew = max(os.path.getmtime(h) for h in hdrs)
     extra = os.environ.get("QN_HIPCC_FLAGS", "").split()          # A/B builds (-DQN_...)
     key = hashlib.sha1(" ".join(extra).encode()).hexdigest()[:10] if extra else ""
@@ -98,148 +152,17 @@ def lib():
     if not os.path.exists(path):
         raise QuinnAmdError(f"{path} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-    # torch ships its own HIP runtime (torch/lib/libamdhip64.so, same SONAME as /opt/rocm's).
-    # It must be the one already mapped when this library is loaded, otherwise the process ends
-    # up with two runtimes and ours sees no device / cannot share torch's streams and memory.
-    import torch  # noqa: F401
     L = ctypes.CDLL(path)
-    vp, i32, i64, f64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
-    L.qn_mlp_desc_create.argtypes = [ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(vp)]
-    L.qn_mlp_desc_create.restype = i32
-    L.qn_rnet_desc_create.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32,
-                                      i32, ctypes.POINTER(vp)]
-    L.qn_rnet_desc_create.restype = i32
-    L.qn_rnet_desc_set_uses.argtypes = [vp, ctypes.POINTER(ctypes.c_ubyte), i32]
-    L.qn_rnet_desc_set_uses.restype = i32
-    L.qn_mlp_desc_destroy.argtypes = [vp]
-    L.qn_mlp_desc_destroy.restype = i32
-    L.qn_mlp_num_params.argtypes = [vp]
-    L.qn_mlp_num_params.restype = i64
-    L.qn_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    L.qn_workspace_bytes.restype = sz
-    L.qn_mlp_path.argtypes = [vp, i32, i32, i32, i32]
-    L.qn_mlp_path.restype = i32
-    L.qn_mlp_desc_set_plan_batch.argtypes = [vp, i32]
-    L.qn_mlp_desc_set_plan_batch.restype = i32
-    L.qn_mlp_arith.argtypes = [vp, i32, i32, i32, i32]
-    L.qn_mlp_arith.restype = i32
-    L.qn_mlp_desc_set_path.argtypes = [vp, i32]
-    L.qn_mlp_desc_set_path.restype = i32
-    L.qn_mlp_sse_fwd.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
-    L.qn_mlp_sse_fwd.restype = i32
-    L.qn_mlp_sse_parts.argtypes = [vp, i32, i32, i32]
-    L.qn_mlp_sse_parts.restype = i32
-    L.qn_mlp_sse_fwd_parts.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
-    L.qn_mlp_sse_fwd_parts.restype = i32
-    L.qn_mlp_sse_fwdbwd.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    L.qn_mlp_sse_fwdbwd.restype = i32
-    L.qn_vi_sample_kl.argtypes = [vp, vp, vp, i32, i64, f64, f64, f64, i32, vp, vp, vp, vp]
-    L.qn_vi_sample_kl.restype = i32
-    L.qn_vi_grad.argtypes = [vp, vp, vp, vp, i32, i64, f64, f64, f64, f64, f64, i32, vp, vp, vp]
-    L.qn_vi_grad.restype = i32
-    L.qn_adam_batched.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, f64, f64, f64, f64, f64, i32, vp]
-    L.qn_adam_batched.restype = i32
-    u64 = ctypes.c_uint64
-    L.qn_mcmc_propose.argtypes = [vp, vp, f64, i32, i32, i64, u64, vp, vp, vp]
-    L.qn_mcmc_propose.restype = i32
-    L.qn_mcmc_propose_hist.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, i64, i64, i32, u64, vp, vp, vp]
-    L.qn_mcmc_propose_hist.restype = i32
-    L.qn_mcmc_hist_block_steps.argtypes = []
-    L.qn_mcmc_hist_block_steps.restype = i32
-    L.qn_mcmc_hist_block_coef_bytes.argtypes = [i32, i32]
-    L.qn_mcmc_hist_block_coef_bytes.restype = sz
-    L.qn_mcmc_propose_hist_block.argtypes = [vp, vp, vp, vp, vp, f64, f64, i32, i32, i64, i64, i32, u64, i64, vp, vp, vp, vp, vp]
-    L.qn_mcmc_propose_hist_block.restype = i32
-    L.qn_mcmc_apply_delta.argtypes = [vp, vp, i32, f64, i32, i32, i64, u64, vp, vp, vp]
-    L.qn_mcmc_apply_delta.restype = i32
-    L.qn_mcmc_accept.argtypes = [vp, vp, f64, i32, i32, i32, i64, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                 vp, i32, i64, vp, i32, i32, vp]
-    L.qn_mcmc_accept.restype = i32
-    L.qn_mcmc_accept_propose.argtypes = [vp, vp, f64, i32, i32, i32, i64, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                         vp, vp, vp, i32, i64, vp, i32, vp, f64, vp, i32, f64, vp, i32, i32, vp]
-    L.qn_mcmc_accept_propose.restype = i32
-    L.qn_hmc_parts.argtypes = [i64]
-    L.qn_hmc_parts.restype = i32
-    L.qn_hmc_begin.argtypes = [vp, vp, f64, f64, i32, i32, i64, u64, vp, vp, vp, vp, vp]
-    L.qn_hmc_begin.restype = i32
-    L.qn_hmc_leap.argtypes = [vp, i32, f64, f64, i32, i32, i64, vp, vp, vp, vp]
-    L.qn_hmc_leap.restype = i32
-    L.qn_hmc_accept.argtypes = [vp, vp, vp, vp, vp, f64, i32, i32, i32, i64, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                vp, i32, vp]
-    L.qn_hmc_accept.restype = i32
-    L.qn_hmc_begin_s.argtypes = [vp, vp, f64, vp, vp, i32, i32, i64, u64, vp, vp, vp, vp, vp]
-    L.qn_hmc_begin_s.restype = i32
-    L.qn_hmc_leap_s.argtypes = [vp, i32, f64, vp, vp, i32, i32, i64, vp, vp, vp, vp]
-    L.qn_hmc_leap_s.restype = i32
-    L.qn_hmc_adapt.argtypes = [vp, vp, i32, vp, i32, i32, i64, i32, f64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.qn_hmc_adapt.restype = i32
-    L.qn_hmc_begin_t.argtypes = [vp, vp, f64, vp, vp, vp, i32, i32, i64, u64, vp, vp, vp, vp, vp]
-    L.qn_hmc_begin_t.restype = i32
-    L.qn_hmc_leap_t.argtypes = [vp, i32, f64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]
-    L.qn_hmc_leap_t.restype = i32
-    L.qn_hmc_accept_t.argtypes = [vp, vp, vp, vp, vp, f64, i32, i32, i32, i64, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                  vp, i32, vp, vp]
-    L.qn_hmc_accept_t.restype = i32
-    L.qn_pt_swap.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i32, u64, i32, i32, vp]
-    L.qn_pt_swap.restype = i32
-    L.qn_sg_rows.argtypes = [vp, i32, i32, i32, i32, u64, vp, i64, vp]
-    L.qn_sg_rows.restype = i32
-    L.qn_sg_step.argtypes = [vp, vp, vp, i32, vp, f64, i32, i32, f64, f64, f64, i32, i64, f64, i32, i32, i32, i32, i64, i32, u64,
-                             vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    L.qn_sg_step.restype = i32
-    L.qn_prior_fold.argtypes = [vp, f64, f64, vp, i32, vp, i32, i32, i64, vp]
-    L.qn_prior_fold.restype = i32
-    L.qn_pred_moments.argtypes = [vp, i32, i64, i64, vp, vp, vp]
-    L.qn_pred_moments.restype = i32
-    L.qn_curv_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    L.qn_curv_workspace_bytes.restype = sz
-    L.qn_mlp_curv.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
-    L.qn_mlp_curv.restype = i32
-    L.qn_glm_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    L.qn_glm_workspace_bytes.restype = sz
-    L.qn_mlp_glm_predict.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]
-    L.qn_mlp_glm_predict.restype = i32
-    L.qn_sobolev_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    L.qn_sobolev_workspace_bytes.restype = sz
-    L.qn_mlp_input_jac.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
-    L.qn_mlp_input_jac.restype = i32
-    L.qn_mlp_sobolev_fwdbwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, sz, vp]
-    L.qn_mlp_sobolev_fwdbwd.restype = i32
-    L.qn_swag_step.argtypes = [i32, vp, vp, i32, vp, f64, vp, vp, vp, i32, i32, i64, i32, i64, vp]
-    L.qn_swag_step.restype = i32
-    L.qn_swag_sample.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, i64, i32, vp, vp]
-    L.qn_swag_sample.restype = i32
-    pi64 = ctypes.POINTER(i64)
-    L.qn_kron_layout.argtypes = [vp, pi64, pi64, pi64, pi64, pi64]
-    L.qn_kron_layout.restype = i32
-    L.qn_kron_workspace_bytes.argtypes = [vp, i32, i32]
-    L.qn_kron_workspace_bytes.restype = sz
-    L.qn_mlp_kron_factors.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
-    L.qn_mlp_kron_factors.restype = i32
-    L.qn_kron_glm_workspace_bytes.argtypes = [vp, i32, i32]
-    L.qn_kron_glm_workspace_bytes.restype = sz
-    L.qn_mlp_kron_glm_predict.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]
-    L.qn_mlp_kron_glm_predict.restype = i32
-    L.qn_kron_sample.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    L.qn_kron_sample.restype = i32
-    L.qn_chain_stats_workspace_bytes.argtypes = [i32, i64, i64, i32, i64]
-    L.qn_chain_stats_workspace_bytes.restype = sz
-    L.qn_chain_stats.argtypes = [vp, i32, i32, i64, i64, i64, i32, i64, vp, vp, sz, vp]
-    L.qn_chain_stats.restype = i32
-    L.qn_pred_score_workspace_bytes.argtypes = [i64, i64, i32]
-    L.qn_pred_score_workspace_bytes.restype = sz
-    L.qn_pred_score.argtypes = [vp, vp, i32, vp, i64, i64, f64, i32, vp, vp, sz, vp]
-    L.qn_pred_score.restype = i32
-    L.qn_debug_tanh.argtypes = [vp, vp, i64, vp]
-    L.qn_debug_tanh.restype = i32
-    L.qn_debug_tanh_finite.argtypes = [vp, vp, i64, vp]
-    L.qn_debug_tanh_finite.restype = i32
-    L.qn_debug_tanh_table.argtypes = [vp, vp, i64, i32, vp]
-    L.qn_debug_tanh_table.restype = i32
-    L.qn_last_error.restype = ctypes.c_char_p
-    L.qn_version.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in FUNCTIONS.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+def stream(dev=None):
+    """The current torch stream of the device, as the C ABI takes it."""
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def check(rc, what):

@@ -1,7 +1,6 @@
 """What the device samplers (`DeviceAMCMC`, `DeviceHMC`, `DeviceMALA`, `DeviceSGHMC`, `DeviceSGLD`) share: the engine's identity
 (operator, noise level, optional Gaussian weight prior, seed, global id of the first chain), the per-run state the accept kernel maintains, the result dict, and `run`, which drives a
 sampler's step generator (`_run_gen`) for all chains at once or for groups of chains side by side on their own HIP streams."""
-import ctypes
 
 import numpy as np
 import torch
@@ -43,7 +42,7 @@ class DeviceEngine:
         self._const = (n / 2) * np.log(2 * np.pi) + n * np.log(self.sigma)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return _lib.stream(self.dev)
 
     @staticmethod
     def _step_ptr(s):

@@ -10,7 +10,6 @@ chains, and the batch-means estimate of the effective sample size (Flegal & Jone
 of floor(sqrt(n)) draws.  Both need one pass and neither a sort nor an FFT.  Rank-normalised / folded R-hat (Vehtari et
 al. 2021) and autocorrelation-based ESS are out of scope.  The reference runs one chain and has no counterpart.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -49,7 +48,7 @@ def _device_stats(t, t0, nbatch, blen):
     ws = torch.empty(need // 8, dtype=torch.float64, device=t.device)
     qdt = _lib.QN_F32 if t.dtype == torch.float32 else _lib.QN_F64
     with torch.cuda.device(t.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+        st = _lib.stream(t.device)
         _lib.check(L.qn_chain_stats(t.data_ptr(), qdt, C, T, K, t0, nbatch, blen, stats.data_ptr(), ws.data_ptr(), need, st),
                    "qn_chain_stats")
     return stats

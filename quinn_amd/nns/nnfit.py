@@ -14,7 +14,6 @@ Two execution modes
     the loss evaluated by the HIP kernels inside the callable and `qn_adam_batched` as optimiser.
 """
 import copy
-import ctypes
 import sys
 
 import numpy as np
@@ -39,7 +38,7 @@ def adam_step(W, G, m, v, lr, step, gscale=1.0, wd=0.0, beta1=0.9, beta2=0.999, 
     L = _lib.lib()
     B, p = W.shape
     qdt = _lib.QN_F64 if G.dtype == torch.float64 else _lib.QN_F32
-    st = ctypes.c_void_p(torch.cuda.current_stream(W.device).cuda_stream)
+    st = _lib.stream(W.device)
     with torch.cuda.device(W.device):
         _lib.check(L.qn_adam_batched(W.data_ptr(), G.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(), B, p,
                                      qdt, gscale, wd, beta1, beta2, eps, step, st), "qn_adam_batched")

@@ -26,11 +26,6 @@ def _ptr(t, rows=None):
     return (t if rows is None else t[rows]).data_ptr()
 
 
-def _stream(dev):
-    """The current torch stream of the device, as the C ABI takes it."""
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 @dataclass(frozen=True)
 class MLPArch:
     """dims = (d, h_1, ..., h_L, o); flat layout [W_0, b_0, W_1, b_1, ...] with W row-major
@@ -357,7 +352,7 @@ class BatchedMLP:
         three arguments of the C entry points."""
         bc, nbytes = self._fit_chunk(B, query, name, zero_ok)
         ws = self._workspace(nbytes)
-        tail = (ws.data_ptr(), ws.numel(), _stream(self.device))
+        tail = (ws.data_ptr(), ws.numel(), _lib.stream(self.device))
         with torch.cuda.device(self.device):
             for b0 in range(0, B, bc):
                 b1 = min(B, b0 + bc)
@@ -434,7 +429,7 @@ class BatchedMLP:
         with torch.cuda.device(self.device):
             _lib.check(self._L.qn_mlp_sse_fwd_parts(self._desc, self.qdt, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
                                                     None, B, N, N, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    _stream(self.device)), "qn_mlp_sse_fwd_parts")
+                                                    _lib.stream(self.device)), "qn_mlp_sse_fwd_parts")
         return out
 
     def sse_grad(self, W, row_idx=None, out=None):
@@ -463,7 +458,7 @@ class BatchedMLP:
             return
         with torch.cuda.device(self.device):
             _lib.check(self._L.qn_prior_fold(W.data_ptr(), float(lam), float(c0), _ptr(grad), gdt, _ptr(sse), int(sse_stride),
-                                             C, p, _stream(self.device)), "qn_prior_fold")
+                                             C, p, _lib.stream(self.device)), "qn_prior_fold")
 
     def sse_pred(self, W, row_idx=None):
         s, pr, _ = self._call(W, row_idx, True, False)
@@ -497,7 +492,7 @@ class BatchedMLP:
         ws = self._workspace(nbytes)
         with torch.cuda.device(self.device):
             _lib.check(self._L.qn_mlp_curv(self._desc, code, Wt.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(), _ptr(ridx), B,
-                                           self.N, Nb, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(self.device)),
+                                           self.N, Nb, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream(self.device)),
                        "qn_mlp_curv")
         return out
 
@@ -819,7 +814,7 @@ def swag_step(mode, W, G=None, lr=None, gscale=1.0, m1=None, m2=None, D=None, sl
         K = D.shape[1]
     with torch.cuda.device(W.device):
         _lib.check(_lib.lib().qn_swag_step(int(mode), _ptr(W), _ptr(G), gdt, _ptr(lr), float(gscale), _ptr(m1), _ptr(m2), _ptr(D),
-                                           K, int(slot), int(n), B, p, _stream(W.device)), "qn_swag_step")
+                                           K, int(slot), int(n), B, p, _lib.stream(W.device)), "qn_swag_step")
 
 
 def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
@@ -843,7 +838,7 @@ def swag_sample(mean, diag, D, js, z1, z2, drift, theta=None):
     _f64_rows(theta, "theta", M, p)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().qn_swag_sample(mean.data_ptr(), diag.data_ptr(), _ptr(D), K, jsd.data_ptr(), z1d.data_ptr(),
-                                             _ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), _stream(dev)),
+                                             _ptr(z2d), M, B, p, int(bool(drift)), theta.data_ptr(), _lib.stream(dev)),
                    "qn_swag_sample")
     return theta
 
@@ -875,7 +870,7 @@ def kron_sample(arch, mean, UA, US, Dih, js, Z, out=None, op=None):
         if out is None:
             out = torch.empty(M, p, dtype=torch.float64, device=dev)
         _f64_rows(out, "out", M, p)
-        st = _stream(dev)
+        st = _lib.stream(dev)
         with torch.cuda.device(dev):
             for m0 in range(0, M, 65535):                         # draws, one per blockIdx.y: no workspace, nothing to fit
                 m1 = min(M, m0 + 65535)

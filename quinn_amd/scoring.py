@@ -8,7 +8,6 @@ of a Gaussian mixture is the closed form of Grimit et al. (Q. J. R. Meteorol. So
 O(M^2 K) evaluations.  PSIS-LOO, rank histograms and energy scores across outputs are out of scope.  The reference has no
 counterpart; the per-entry definitions are in include/quinn_amd.h at `qn_pred_score`.
 """
-import ctypes
 
 import numpy as np
 import torch
@@ -67,7 +66,7 @@ def score_rows(F, y, noise, V=None, what=WHAT_ALL):
     ws = torch.empty(need // 8, dtype=torch.float64, device=F.device)
     qdt = _lib.QN_F32 if F.dtype == torch.float32 else _lib.QN_F64
     with torch.cuda.device(F.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(F.device).cuda_stream)
+        st = _lib.stream(F.device)
         _lib.check(L.qn_pred_score(F.data_ptr(), V.data_ptr() if V is not None else None, qdt, y.data_ptr(), M, K,
                                    float(noise), what, out.data_ptr(), ws.data_ptr(), need, st), "qn_pred_score")
     return out

@@ -7,7 +7,6 @@ variance / covariance over that ensemble.  The matplotlib helpers of the referen
 path and are not reproduced.
 """
 import copy
-import ctypes
 import sys
 
 import numpy as np
@@ -88,7 +87,7 @@ class QUiNNBase():
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().qn_pred_moments(y.data_ptr(), qdt, M, nx * nout, mean.data_ptr(),
                                                   var.data_ptr() if var is not None else None,
-                                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qn_pred_moments")
+                                                  _lib.stream(dev)), "qn_pred_moments")
         ymean = mean.cpu().numpy()
         if msc == 2:
             yc = y.double() - mean                                   # (M, N, o)
@@ -137,7 +136,7 @@ class QUiNNBase():
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().qn_pred_moments(J.data_ptr(), _lib.QN_F64, M, K, mean.data_ptr(),
                                                   var.data_ptr() if var is not None else None,
-                                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "qn_pred_moments")
+                                                  _lib.stream(dev)), "qn_pred_moments")
         return mean.cpu().numpy(), (var.cpu().numpy() if var is not None else None)
 
     # -- scores of the predictive against data (qn_pred_score) ---------------------------------------------

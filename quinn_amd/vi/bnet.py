@@ -15,7 +15,6 @@ are drawn on the host from torch's global CPU generator, sample by sample and pa
 parameter tensor (the reference's consumption order, rvs.py:107); `rng='device'` draws on the GPU.
 """
 import copy
-import ctypes
 
 import numpy as np
 import torch
@@ -55,7 +54,7 @@ class _ViLoss(torch.autograd.Function):
         dtheta = torch.empty(2 * p, dtype=torch.float64, device=mu.device)
         gw_scale = 0.5 / (ctx.nsam * ctx.o * ctx.datanoise ** 2)      # dNLL/dSSE_s, bnet.py:215
         kl_scale = 1.0 / ctx.num_batches
-        st = ctypes.c_void_p(torch.cuda.current_stream(mu.device).cuda_stream)
+        st = _lib.stream(mu.device)
         with torch.cuda.device(mu.device):
             _lib.check(L.qn_vi_grad(mu.data_ptr(), rho.data_ptr(), eps.data_ptr(), gW.data_ptr(), ctx.nsam, p,
                                     bnet.pi, bnet.sigma1, bnet.sigma2, gw_scale, kl_scale, bnet.op.qdt,
@@ -130,7 +129,7 @@ class BNet(torch.nn.Module):
         W = torch.empty(S, self.p, dtype=self.op.tdt, device=self.device)
         lq = torch.empty(S, dtype=torch.float64, device=self.device)
         lp = torch.empty(S, dtype=torch.float64, device=self.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = _lib.stream(self.device)
         with torch.cuda.device(self.device):
             _lib.check(L.qn_vi_sample_kl(mu.contiguous().data_ptr(), rho.contiguous().data_ptr(), eps.data_ptr(), S,
                                          self.p, self.pi, self.sigma1, self.sigma2, self.op.qdt, W.data_ptr(),

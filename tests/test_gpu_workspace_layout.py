@@ -4,7 +4,6 @@ workspace its size query asks for, computes the same bits in a larger one and re
 One network per family (the NETS of tests/golden/gen_golden_sse_ws_sizes.py, whose CPU test checks that each reaches its family)
 at B = 3 members -- odd: the XCD-aware grid is padded -- and 70 rows: above 64 and no multiple of 16 or 64, so the stashes' row
 stride differs from the row count, the int8 weight gradient has a float64 tail and the last row split is ragged."""
-import ctypes
 import os
 import sys
 
@@ -42,7 +41,7 @@ def _call(L, h, grad, W, X, Y, o, ws, ws_bytes):
     """One call with `ws_bytes` of the buffer `ws` declared: (return code, sse, pred, grad or None)."""
     sse = torch.zeros(B, dtype=torch.float64, device="cuda")
     pred = torch.zeros(B, ROWS, o, dtype=torch.float64, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _lib.stream()
     head = (h, _lib.QN_F64, W.data_ptr(), X.data_ptr(), Y.data_ptr(), None, B, ROWS, ROWS, sse.data_ptr(), pred.data_ptr())
     if grad:
         g = torch.zeros_like(W)

@@ -12,7 +12,6 @@ median over `windows` such windows.  The yardstick is a float64 device-to-device
 of up to 8 GB in the same process; MI355X_MICROARCH.md gives ~6.3 TB/s for it.
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -75,7 +74,7 @@ def bench_shape(shape, reps, windows, copy_bps, nburn_frac):
     need = L.qn_chain_stats_workspace_bytes(C, T, K, nbatch, blen)
     ws = torch.empty(need // 8, dtype=torch.float64, device="cuda")
     stats = torch.empty(C, 6, K, dtype=torch.float64, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _lib.stream()
 
     def call():
         _lib.check(L.qn_chain_stats(x.data_ptr(), _lib.QN_F64, C, T, K, t0, nbatch, blen, stats.data_ptr(), ws.data_ptr(),

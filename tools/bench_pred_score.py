@@ -17,7 +17,6 @@ child process of its own under a time limit, and the first child that fails ends
 Times are device-event times of `reps` back-to-back calls after a warm-up call, median over `windows` such windows.
 """
 import argparse
-import ctypes
 import json
 import os
 import subprocess
@@ -51,7 +50,7 @@ def timed(fn, reps, windows):
 
 def bench_one(M, K, reps, windows):
     L = _lib.lib()
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _lib.stream()
     gen = torch.Generator(device="cuda").manual_seed(M * 100003 + K)
     mu = torch.randn(K, dtype=torch.float64, device="cuda", generator=gen)
     y = mu + 0.7 * torch.randn(K, dtype=torch.float64, device="cuda", generator=gen)

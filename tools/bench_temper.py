@@ -58,7 +58,7 @@ st = {'cur': torch.randn(C, p, dtype=f64, device=dev), 'g': torch.randn(C, p, dt
       'chain': torch.zeros(C, nm + 1, p, dtype=f64, device=dev), 'rid': torch.zeros(2, C, dtype=torch.int32, device=dev),
       'rep': torch.zeros(C, 3, dtype=torch.int32, device=dev), 'acc': torch.zeros(C, dtype=torch.int64, device=dev),
       'try': torch.zeros(C, dtype=torch.int64, device=dev), 'step': torch.ones(2, dtype=torch.int64, device=dev)}
-stream = torch.cuda.current_stream().cuda_stream
+stream = _lib.stream()
 
 
 def swap_time(cur_lp, nrep=200):
