@@ -420,6 +420,50 @@ int qn_sg_step(double* theta, double* v, const void* grad, int dtype, const doub
 int qn_prior_fold(const double* W, double lam, double c0, void* grad, int gdtype, double* sse, int sse_stride, int C, int64_t p,
                   void* stream);
 
+/* Elliptical slice sampling on the device (Murray, Adams & MacKay 2010; build-only, the reference has no such sampler) for
+ * the target L(w) N(w; 0, priorsigma^2 I), log L = gs sse + const, gs = -0.5 / sigma^2: no step size, no warm-up, only forward
+ * calls.  The chains' steps are ASYNCHRONOUS: every chain has its own step t and shrink count j, and a launch of qn_ess_iter
+ * either shrinks a chain's bracket or, its pending proposal accepted, starts the chain's next step in the same launch.  A run
+ * is qn_ess_begin, then (qn_mlp_sse_fwd_parts on prop, qn_ess_iter) until every chain has made nmcmc steps; qn_prior_fold is
+ * NOT launched (the ellipse carries the prior, the slice test sees the likelihood).  quinn_amd/mcmc/ess.py restates the rule.
+ * Philox4x32-10 keyed by (seed, stream = the chain's step t, counter = [GLOBAL chain id = chain0 + c : 24][purpose : 4]
+ * [index : 36]): purpose 7 = the ellipse partner (index = column pair; the float32-transcendental normals of the HMC momenta,
+ * ~1e-6 relative accuracy), purpose 8 = the angle uniforms (index 0: start of the step; index j + 1: shrink j + 1).
+ * Per-chain state, double-buffered by the launch parity the caller alternates (slot `parity` is read, slot 1 - parity
+ * written -- copied for done chains and unchanged entries; slot 0 holds the state after qn_ess_begin):
+ *     es [2, C, 6] float64 = (theta, tmin, tmax, logy, sse_cur, lp_cur)      ei [2, C, 4] int64 = (t, j, ntrunc, nevals)
+ *     best_lp [2, C]      sq_parts [2, C, qn_hmc_parts(p)]: partial sums of squares of the pending proposal (fixed order, a
+ *     function of p alone; the next launch adds them left to right for the log-prior)
+ * and cur, nu, prop [C, p] float64, updated in place (an element belongs to one thread).  prop_op (optional, dtype QN_F32
+ * only): every new proposal also as float32 [C, p], what a float32 operator's next forward reads.
+ *
+ * qn_ess_begin: start of step 0 of every chain from cur and sse_cur [C]:
+ *     nu = priorsigma z;  theta = 2 pi u1;  logy = gs sse_cur + log u2;  tmin = theta - 2 pi;  tmax = theta;  j = 0;
+ *     prop = cur cos(theta) + nu sin(theta)                   (u1, u2: words (0, 1) and (2, 3) of the purpose-8 block, index 0)
+ *   writes nu, prop, prop_op, slot 0 of sq_parts, es (sse_cur and lp_cur [C] copied from the arguments) and ei (zeros).
+ * qn_ess_iter: with sse_prop [C, nparts] (summed left to right) the SSE of the pending proposals, for every chain with t < nmcmc:
+ *   - accept iff sse_prop is finite and gs sse_prop > logy (NaN: no): cur <- prop, sse_cur <- sse_prop,
+ *       lp_cur = (gs sse_prop - (n_rows / 2) log 2 pi - n_rows log sigma) + (-0.5 |prop|^2 / priorsigma^2 - (p / 2) log(2 pi priorsigma^2)),
+ *     chain[c, t + 1, :] <- prop (chain [C, nmcmc + 1, p] or NULL), lps[c, t + 1] = lp_cur, nev[c, t + 1] = j + 1 (int32
+ *     [C, nmcmc + 1]), best [C, p] <- prop where lp_cur >= best_lp, t += 1; if t < nmcmc the next step starts as in qn_ess_begin;
+ *   - else, j + 1 < max_shrink: theta < 0 ? tmin = theta : tmax = theta; theta = tmin + u (tmax - tmin) (u: words (0, 1) of
+ *     the purpose-8 block, index j + 1); j += 1; prop = cur cos(theta) + nu sin(theta);
+ *   - else (truncation): the chain stays: chain[c, t + 1, :] <- cur, lps[c, t + 1] = lp_cur, nev[c, t + 1] = max_shrink,
+ *     ntrunc += 1, t += 1, and the next step starts;
+ *   nevals += 1 in every case.  A chain with t == nmcmc is done: none of its arrays is read or written, its scalars are copied.
+ * cos / sin of the angle are float64.  No atomics, no fences: equal inputs give equal bits, and a chain's result does not
+ * depend on C, on its place in the launch, or on what the other chains do.
+ * QN_EINVAL with a message, before any pointer is touched: C outside 1 .. 65535; chain0 < 0; p < 1; nmcmc, max_shrink, nparts
+ *   or n_rows < 1; priorsigma or sigma not > 0 or not finite; a parity other than 0 / 1; a dtype other than the two; prop_op with
+ *   QN_F64; a NULL pointer other than chain / prop_op. */
+int qn_ess_begin(const double* cur, const double* sse_cur, const double* lp_cur, double sigma, double priorsigma, int C,
+                 int chain0, int64_t p, uint64_t seed, double* nu, double* prop, void* prop_op, int dtype, double* sq_parts,
+                 double* es, int64_t* ei, void* stream);
+int qn_ess_iter(const double* sse_prop, int nparts, double sigma, double priorsigma, int n_rows, int max_shrink, int C, int chain0,
+                int64_t p, int nmcmc, uint64_t seed, double* cur, double* nu, double* prop, void* prop_op, int dtype, double* best,
+                double* best_lp, double* chain, double* lps, int32_t* nev, double* sq_parts, double* es, int64_t* ei, int parity,
+                void* stream);
+
 /* Moments of a predictive ensemble on the device (QUiNNBase.predict_mom_sample, quinn/solvers/quinn.py:75-104):
  * Y [M, K] dtype = M members x K = N * o prediction entries as qn_mlp_sse_fwd writes them ([B, Nb, o] with B = M);
  * mean_out [K], var_out [K] (unbiased, ddof = 1; NULL to skip; needs M >= 2), float64.  The per-output covariance of

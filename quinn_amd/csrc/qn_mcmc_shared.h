@@ -1,4 +1,4 @@
-// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_leap.hip, qn_hmc_adapt.hip, qn_temper.hip, qn_sgmcmc.hip, qn_prior.hip): the Philox4x32-10 generator and
+// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_leap.hip, qn_hmc_adapt.hip, qn_temper.hip, qn_sgmcmc.hip, qn_prior.hip, qn_ess.hip): the Philox4x32-10 generator and
 // its counter layout, the normal / uniform transforms, the 8-byte aligned pair accesses and the geometry + fixed-order block
 // sum of the HMC elementwise kernels.  Everything is internal linkage: each translation unit gets its own copy.
 #pragma once
@@ -29,7 +29,9 @@ struct Philox {
 // Philox counter of one draw: [global chain id : 24][purpose : 4][index : 36].  The chain id is GLOBAL
 // (chain0 + local index), so a chain's random numbers do not depend on how chains are split over launches /
 // ranks.  purposes: 0 elementwise normals (index = column pair), 1 per-chain scalar normal, 2 accept uniform,
-// 3 history coefficients (index = row pair)
+// 3 history coefficients (index = row pair); 4 minibatch rows and 5 step noise (qn_sgmcmc.hip); 6 the exchange uniform
+// (qn_temper.hip); 7 the ellipse partner (index = column pair) and 8 the angle uniforms (index = shrink count) of elliptical
+// slice sampling (qn_ess.hip).  9-15 are free
 __device__ __forceinline__ uint64_t ctr_of(int chain, int purpose, uint64_t index) {
     return ((uint64_t)chain << 40) | ((uint64_t)purpose << 36) | (index & 0xFFFFFFFFFull);
 }

@@ -25,6 +25,8 @@ from ..mcmc.device_amcmc import DeviceAMCMC
 from ..mcmc.device_hmc import DeviceHMC
 from ..mcmc.device_mala import DeviceMALA
 from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
+from ..mcmc.device_ess import DeviceESS
+from ..mcmc.ess import check_ess_args
 from ..mcmc import diagnostics as diag
 from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
@@ -33,8 +35,9 @@ from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run
 from .quinn import QUiNNBase
 
 # fit(engine='device'): sampler -> class
-DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 'sgld': DeviceSGLD, 'sghmc': DeviceSGHMC}
-DEVICE_ONLY = ('sgld', 'sghmc')                  # stochastic-gradient samplers: no host counterpart
+DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 'sgld': DeviceSGLD, 'sghmc': DeviceSGHMC,
+                  'ess': DeviceESS}
+DEVICE_ONLY = ('sgld', 'sghmc', 'ess')           # stochastic-gradient samplers, elliptical slice sampling: no host counterpart
 
 
 class NN_MCMC(QUiNNBase):
@@ -192,6 +195,12 @@ class NN_MCMC(QUiNNBase):
             ('constant' | 'cyclic'), cycles and explore_frac (cyclic: cosine cycles over the run; the head of each cycle runs
             without noise), temperature (default 1), use_graph, groups.  There is no accept test ('accrate' and 'alphas' are 1)
             and 'logpost' is the minibatch estimate of each stored state's log-posterior.
+            sampler='ess' (engine='device' only; `quinn_amd.mcmc.device_ess`): elliptical slice sampling.  Needs priorsigma
+            (the ellipse is drawn from the prior); no step size, no warm-up, forward calls only.  sampler_params: max_shrink
+            (proposals per step before the step is truncated and the chain stays; default 32), block (iterations enqueued
+            between two looks at the chains' step counters; default 32), groups.  The chains advance asynchronously on the
+            device; `mcmc_results` also holds 'nev' `(C, nmcmc + 1)` (forward evaluations per step), 'ntrunc' and 'nevals'
+            `(C,)`; 'accrate' is 1 - ntrunc / nmcmc and 'alphas' is 1.
             gtrn `(N, d)` | `(N, o, d)` with gradnoise (sigma_g): observed input gradients as a second Gaussian likelihood
             term, log-posterior -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2)
             - N o d (log sigma_g + log(2 pi) / 2) with gsse = sum (dM/dx - gtrn)^2; engine='host' only (the device engines'
@@ -209,7 +218,13 @@ class NN_MCMC(QUiNNBase):
         self.diagnostics = None
         priorsigma = check_priorsigma(priorsigma)
         if sampler in DEVICE_ONLY and engine != 'device':
-            raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host SG sampler)")
+            raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host engine for it)")
+        if sampler == 'ess':                     # (before any device is touched)
+            sp = dict(sampler_params or {})
+            if priorsigma is None:
+                raise ValueError("sampler='ess' needs priorsigma: elliptical slice sampling draws from the Gaussian weight prior "
+                                 "N(0, priorsigma^2 I); pass fit(..., priorsigma=s) with s > 0")
+            check_ess_args(priorsigma, sp.get('max_shrink', 32), sp.get('block', 32))
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
         ntrn_, outdim = ytrn.shape
         assert xtrn.shape[0] == ntrn_
@@ -263,7 +278,7 @@ class NN_MCMC(QUiNNBase):
             lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
             seed0 = seeds[0] if seeds else 0
             if sampler not in DEVICE_ENGINES:
-                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld' and 'sghmc'")
+                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld', 'sghmc' and 'ess'")
             # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
             nrounds = None
             if sampler_params.get('ladder') is not None and sampler in ('hmc', 'mala'):
@@ -279,6 +294,9 @@ class NN_MCMC(QUiNNBase):
             else:
                 res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)),
                                     nrounds=nrounds)
+                if sampler == 'ess':
+                    res.update(nev=np.zeros((0, nmcmc + 1), dtype=np.int32), ntrunc=np.zeros(0, dtype=np.int64),
+                               nevals=np.zeros(0, dtype=np.int64))
             if diagnostics:
                 # from the engine's device tensors, before they are downloaded (or not: gather_chain='none'); of a
                 # replica-exchange run the cold chains only (rung 0 of every ladder: shards are whole ladders)
