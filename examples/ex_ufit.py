@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|ess|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -19,6 +19,8 @@ chains; MLP network),
 run without a prior and a `laplace_ggn` fit with the same `priorsigma` -- the Laplace approximation of the posterior it samples,
 `ess` is elliptical slice sampling on the device with the same `priorsigma=1.0` (`engine='device'`; MLP network): no step size, forward
 calls only; it prints the forward evaluations a step took,
+`nuts` is the No-U-Turn sampler on the device (`engine='device'`; MLP network): no trajectory length, the step size dual-averaged
+over the first tenth of the run; it prints the depth and the leapfrogs a step took,
 and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
@@ -48,7 +50,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -57,7 +59,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'ess'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -109,6 +111,15 @@ def main(meth, quick=False, mlp=False):
         others['laplace_ggn, priorsigma = %g' % ps] = (yl.mean(axis=0)[:, 0], yl.std(axis=0, ddof=1)[:, 0])
         for label, (m, s) in others.items():
             print(f"  {label}: predictive std on the grid " + " ".join(f"{v:.3f}" for v in s))
+    elif meth == 'nuts':
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='nuts', engine='device',
+                  sampler_params={'epsilon': 1e-3, 'adapt': 1000 // k, 'max_depth': 8}, seeds=range(8), diagnostics=True)
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+        r = uqnet.mcmc_results
+        print(f"  depth per step: mean {r['depth'][:, 1:].mean():.2f}, max {r['depth'].max()}; leapfrogs per step: mean "
+              f"{r['nleap'][:, 1:].mean():.2f}; divergent steps {r['ndiv'].sum()}, stopped by max_depth {r['ntreedepth'].sum()}; "
+              f"step sizes {r['epsilon'].min():.3g} .. {r['epsilon'].max():.3g}; acceptance statistic {r['accrate'].mean():.3f}")
     elif meth == 'ess':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='ess', engine='device',
@@ -162,7 +173,7 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess'):
+    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess', 'nuts'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]

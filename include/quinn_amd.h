@@ -464,6 +464,74 @@ int qn_ess_iter(const double* sse_prop, int nparts, double sigma, double priorsi
                 double* best_lp, double* chain, double* lps, int32_t* nev, double* sq_parts, double* es, int64_t* ei, int parity,
                 void* stream);
 
+/* The No-U-Turn sampler on the device (Hoffman & Gelman 2014 with the multinomial weights of Betancourt 2017: biased
+ * progressive sampling between subtrees, uniform within a subtree; build-only, the reference has no such sampler): no
+ * trajectory length.  The ITERATIVE form: one leapfrog, that is one gradient call, per iteration; every U-turn test of the
+ * trajectory's binary tree is made from checkpoints.  The chains' steps are ASYNCHRONOUS: every chain has its own step t, its
+ * own tree (d doublings merged, leaf i of the subtree being built, direction v) and ends its step when ITS tree does.  A run
+ * is qn_nuts_begin, then (qn_mlp_sse_fwdbwd at q, qn_prior_fold if there is a prior, qn_nuts_iter) until every chain has made
+ * nmcmc steps.  quinn_amd/mcmc/nuts.py states the rule in full and restates it in numpy; its recursive builder is the authority.
+ * Whitened momenta u = scale * r as in qn_hmc_begin_s (scale [C, p] or NULL = 1): kinetic energy |u|^2 / 2, U-turn tests are
+ * dot products.  lp = gs sse - (n_rows / 2) log 2 pi - n_rows log sigma, force gs g, gs = -0.5 / sigma^2, g = d sse / d w float64.
+ * With hk = v ((eps / 2) gs), dr = v eps: u_half = u + (hk scale) g, q' = q + (dr scale) u_half, u' = u_half + (hk scale) g'
+ * -- one rounding per operation, no contraction: the elementwise results equal numpy's bit for bit.
+ * Philox4x32-10 keyed by (seed, stream = the chain's step t, counter = [GLOBAL chain id = chain0 + c : 24][purpose : 4]
+ * [index : 36]): purpose 9 = the momenta (index = column pair; the float32-transcendental normals of the HMC momenta), purpose
+ * 10 = the scalar uniforms, index (kind << 32) | n: kind 0 the direction of doubling n (v = +1 iff u < 0.5), kind 1 the merge
+ * of doubling n, kind 2 the leaf whose n_leap was n before the increment.
+ * Per-chain state, double-buffered by the launch parity the caller alternates (slot `parity` is read, slot 1 - parity
+ * written -- copied for done chains; slot 0 holds the state after qn_nuts_begin):
+ *     es [2, C, 12] float64 = (eps, mu, hbar, logbar, H0, logW, logW_sub, sum_a, sse_cur, lp_cur, sse_sub, lp_sub)
+ *         (eps: the chain's step size, written only by the in-kernel dual averaging; H0 is formed at a step's first leaf)
+ *     ei [2, C, 8] int64 = (t, d, i, v, n_leap, ndiv, ntreedepth, ngrad)        best_lp [2, C]
+ *     zz_parts [2, C, qn_hmc_parts(p)]: partial sums of squares of a step's momenta (the next launch adds them for H0)
+ * and the float64 vectors, updated in place (an element belongs to one thread): cur, gcur (the tree's proposal and its
+ * gradient -- at a step's start and end the chain's current point), the edges ql, ul, gl, qr, ur, gr, rho, the pending point q
+ * with the half-kicked momentum u, of the subtree rho_sub, sub_q, sub_g and the checkpoints ck_u, ck_rho [C, max_depth, p], and
+ * best: (15 + 2 max_depth) p doubles per chain, the gradient array of the operator and the stored chain not counted.
+ * dot_parts [C, qn_hmc_parts(p), 27] is scratch of one call (fixed-order partial sums: slot 0 |u'|^2; 1 + 2k, 2 + 2k checkpoint
+ * k; 25, 26 the tree), added left to right: the order depends on p alone.
+ *
+ * qn_nuts_begin: start of step 0 of every chain from cur, gcur [C, p] and sse_cur [C] with the step sizes eps0 [C]:
+ *     z ~ N(0, I); both edges = (cur, z, gcur), rho = z, logW = 0, d = i = n_leap = 0, sum_a = 0, v = direction of doubling 0,
+ *     u = z + (hk scale) gcur, q = cur + (dr scale) u; es (mu = log(10 eps0), hbar = logbar = 0), ei, best_lp = lp_cur, slot 0.
+ * qn_nuts_iter: with sse [C] and grad [C, p] of the pending points q, for every chain with t < nmcmc -- leaf i of 2^d:
+ *     u' = u + (hk scale) grad; rho_sub = (i == 0 ? u' : rho_sub + u'); dE = (-lp' + |u'|^2 / 2) - H0, NaN counted as +inf;
+ *     sum_a += min(1, exp(-dE)); n_leap += 1; ngrad += 1; the leaf is divergent iff dE > 1000: the step ends, ndiv += 1;
+ *     logW_sub = (i == 0 ? -dE : logaddexp(logW_sub, -dE)); with probability exp(-dE - logW_sub) the leaf becomes the subtree's
+ *     proposal (sub_q, sub_g, sse_sub, lp_sub);
+ *     i even, i + 1 < 2^d: ck_u[k] = u', ck_rho[k] = rho_sub for k = popcount(i >> 1) =: idx_max;
+ *     i odd: for k = idx_max .. idx_max - (trailing one bits of i) + 1, r = (rho_sub - ck_rho[k]) + ck_u[k]: the subtree turns
+ *     iff r . ck_u[k] <= 0 or r . u' <= 0, and the step ends;
+ *     i + 1 < 2^d: i += 1, the next leapfrog starts from the leaf (u, q as above);
+ *     i + 1 == 2^d: with probability min(1, exp(logW_sub - logW)) (cur, gcur, sse_cur, lp_cur) <- the subtree's proposal;
+ *     logW = logaddexp(logW, logW_sub); d += 1; with rho' = rho + rho_sub and the edge on side v = the leaf, the step ends if
+ *     rho' . ul <= 0 or rho' . ur <= 0, or else if d == max_depth (ntreedepth += 1); otherwise rho = rho', the edge is stored, a
+ *     new direction is drawn and leaf 0 starts from that side's edge.  The classic criterion: Stan's later extra checks across
+ *     adjacent subtrees are not made.
+ *   Step end: chain[c, t + 1, :] <- cur (chain [C, nmcmc + 1, p] or NULL), lps[c, t + 1] = lp_cur, alphas[c, t + 1] = sum_a /
+ *     n_leap, depth[c, t + 1] = the doublings started (d, or d + 1 when the step ended inside a subtree), nleap[c, t + 1] =
+ *     n_leap (int32 [C, nmcmc + 1]); best [C, p] <- cur where lp_cur >= best_lp; if t < adapt, eps is dual-averaged as by
+ *     qn_hmc_adapt (same constants and formula, m = t + 1, a = sum_a / n_leap, NaN counted as 0) and frozen to exp(logbar) at
+ *     t == adapt - 1 (the step size only: no mass windows); t += 1; if t < nmcmc the next step starts as in qn_nuts_begin.
+ *   A chain with t == nmcmc is done: none of its arrays is read or written, its scalars are copied.  (So is a chain whose
+ *   caller-written counters could index outside an array: d outside 0 .. max_depth - 1, i outside 0 .. 2^d - 1, t < 0.)
+ * Two launches (reduce; decide and move) on the qn_hmc_parts(p)-workgroups-per-chain grid.  No atomics, no fences: equal inputs
+ * give equal bits, and a chain's result does not depend on C, on its place in the launch, or on what the other chains do.
+ * QN_EINVAL with a message, before any pointer is touched: C outside 1 .. 65535; chain0 < 0; p < 1; n_rows < 1; nmcmc < 1;
+ *   max_depth outside 1 .. 12; adapt outside 0 .. nmcmc; target_accept outside (0, 1); sigma not > 0 or not finite; a parity
+ *   other than 0 / 1; a NULL pointer other than chain / scale. */
+int qn_nuts_begin(const double* sse_cur, const double* eps0, const double* scale, double sigma, int n_rows, int C, int chain0,
+                  int64_t p, uint64_t seed, const double* cur, const double* gcur, double* ql, double* ul, double* gl, double* qr,
+                  double* ur, double* gr, double* rho, double* q, double* u, double* zz_parts, double* best_lp, double* es,
+                  int64_t* ei, void* stream);
+int qn_nuts_iter(const double* sse, const double* grad, const double* scale, double sigma, int n_rows, int max_depth, int adapt,
+                 double target_accept, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, double* cur, double* gcur,
+                 double* ql, double* ul, double* gl, double* qr, double* ur, double* gr, double* rho, double* q, double* u,
+                 double* rho_sub, double* sub_q, double* sub_g, double* ck_u, double* ck_rho, double* best, double* best_lp,
+                 double* chain, double* lps, double* alphas, int32_t* depth, int32_t* nleap, double* dot_parts, double* zz_parts,
+                 double* es, int64_t* ei, int parity, void* stream);
+
 /* Moments of a predictive ensemble on the device (QUiNNBase.predict_mom_sample, quinn/solvers/quinn.py:75-104):
  * Y [M, K] dtype = M members x K = N * o prediction entries as qn_mlp_sse_fwd writes them ([B, Nb, o] with B = M);
  * mean_out [K], var_out [K] (unbiased, ddof = 1; NULL to skip; needs M >= 2), float64.  The per-output covariance of

@@ -27,6 +27,8 @@ from ..mcmc.device_mala import DeviceMALA
 from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
 from ..mcmc.device_ess import DeviceESS
 from ..mcmc.ess import check_ess_args
+from ..mcmc.device_nuts import DeviceNUTS
+from ..mcmc.nuts import check_nuts_args
 from ..mcmc import diagnostics as diag
 from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
@@ -36,8 +38,9 @@ from .quinn import QUiNNBase
 
 # fit(engine='device'): sampler -> class
 DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 'sgld': DeviceSGLD, 'sghmc': DeviceSGHMC,
-                  'ess': DeviceESS}
-DEVICE_ONLY = ('sgld', 'sghmc', 'ess')           # stochastic-gradient samplers, elliptical slice sampling: no host counterpart
+                  'ess': DeviceESS, 'nuts': DeviceNUTS}
+# stochastic-gradient samplers, elliptical slice sampling, the No-U-Turn sampler: no host counterpart
+DEVICE_ONLY = ('sgld', 'sghmc', 'ess', 'nuts')
 
 
 class NN_MCMC(QUiNNBase):
@@ -150,8 +153,8 @@ class NN_MCMC(QUiNNBase):
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
             datanoise (likelihood sigma), nmcmc, param_ini `(p,)` [or `(C,p)`], sampler
-            ('amcmc' | 'hmc' | 'mala'; build-only, engine='device': 'sgld' | 'sghmc'), sampler_params (dict splatted into
-            the sampler).
+            ('amcmc' | 'hmc' | 'mala'; build-only, engine='device': 'sgld' | 'sghmc' | 'ess' | 'nuts'), sampler_params (dict
+            splatted into the sampler).
         Build-only: nchains (C independent chains in lock-step), seeds (C ints; chain c then
             equals a reference run preceded by np.random.seed(seeds[c])).  With nchains=1 and
             seeds=None the global numpy RNG is used, exactly like the reference.
@@ -201,6 +204,15 @@ class NN_MCMC(QUiNNBase):
             between two looks at the chains' step counters; default 32), groups.  The chains advance asynchronously on the
             device; `mcmc_results` also holds 'nev' `(C, nmcmc + 1)` (forward evaluations per step), 'ntrunc' and 'nevals'
             `(C,)`; 'accrate' is 1 - ntrunc / nmcmc and 'alphas' is 1.
+            sampler='nuts' (engine='device' only; `quinn_amd.mcmc.device_nuts`): the No-U-Turn sampler, multinomial, in whitened
+            momenta.  No trajectory length: a step doubles its trajectory until it turns back on itself.  sampler_params:
+            epsilon (the step size, a scalar or one per chain), mass_scale (None, or `(nchains, p)`: e.g. 'mass_scale' of an
+            'hmc' fit with adapt=K, with its 'epsilon'), max_depth (doublings per step, 1 .. 12; default 10), adapt (warm-up
+            steps of step-size dual averaging; NUTS's own warm-up has no mass windows), target_accept (default 0.8), block,
+            groups.  The chains advance asynchronously on the device; `mcmc_results` also holds 'depth' and 'nleap'
+            `(C, nmcmc + 1)` (doublings and leapfrogs per step), 'ndiv', 'ntreedepth', 'ngrad' and 'epsilon' `(C,)` and 'nwarm';
+            'alphas' is the acceptance statistic of each step and 'accrate' its mean.  float64 operators only; no ladder, no
+            graph capture.
             gtrn `(N, d)` | `(N, o, d)` with gradnoise (sigma_g): observed input gradients as a second Gaussian likelihood
             term, log-posterior -0.5 sse / sigma^2 - 0.5 gsse / sigma_g^2 - N o (log sigma + log(2 pi) / 2)
             - N o d (log sigma_g + log(2 pi) / 2) with gsse = sum (dM/dx - gtrn)^2; engine='host' only (the device engines'
@@ -225,6 +237,10 @@ class NN_MCMC(QUiNNBase):
                 raise ValueError("sampler='ess' needs priorsigma: elliptical slice sampling draws from the Gaussian weight prior "
                                  "N(0, priorsigma^2 I); pass fit(..., priorsigma=s) with s > 0")
             check_ess_args(priorsigma, sp.get('max_shrink', 32), sp.get('block', 32))
+        if sampler == 'nuts':                    # (before any device is touched)
+            sp = dict(sampler_params or {})
+            check_nuts_args(sp.get('epsilon', 0.05), sp.get('max_depth', 10), sp.get('adapt', 0), sp.get('target_accept', 0.8),
+                            sp.get('block', 32), nmcmc)
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
         ntrn_, outdim = ytrn.shape
         assert xtrn.shape[0] == ntrn_
@@ -278,7 +294,8 @@ class NN_MCMC(QUiNNBase):
             lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
             seed0 = seeds[0] if seeds else 0
             if sampler not in DEVICE_ENGINES:
-                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld', 'sghmc' and 'ess'")
+                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld', 'sghmc', 'ess' and "
+                                 "'nuts'")
             # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
             nrounds = None
             if sampler_params.get('ladder') is not None and sampler in ('hmc', 'mala'):
@@ -288,9 +305,18 @@ class NN_MCMC(QUiNNBase):
                                       use_graph=sampler_params.get('use_graph', False)).size
                 check_whole_ladders(R, hi - lo, lo)
                 nrounds = nmcmc // int(sampler_params.get('swap_every', 1))
+            if sampler == 'nuts':                # per-chain step sizes / scales of all chains: this rank's rows
+                for k in ('epsilon', 'mass_scale'):
+                    if np.ndim(sampler_params.get(k)) >= 1:
+                        sampler_params[k] = np.asarray(sampler_params[k], dtype=np.float64)[lo:hi]
             eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, priorsigma=priorsigma, **sampler_params)
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
+            elif sampler == 'nuts':
+                res = empty_results(nmcmc, ini2.shape[1])
+                res.update(depth=np.zeros((0, nmcmc + 1), dtype=np.int32), nleap=np.zeros((0, nmcmc + 1), dtype=np.int32),
+                           ndiv=np.zeros(0, dtype=np.int64), ntreedepth=np.zeros(0, dtype=np.int64),
+                           ngrad=np.zeros(0, dtype=np.int64), epsilon=np.zeros(0), nwarm=nadapt)
             else:
                 res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)),
                                     nrounds=nrounds)
