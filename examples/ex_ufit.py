@@ -50,7 +50,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -59,7 +59,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'hyper', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -111,6 +111,16 @@ def main(meth, quick=False, mlp=False):
         others['laplace_ggn, priorsigma = %g' % ps] = (yl.mean(axis=0)[:, 0], yl.std(axis=0, ddof=1)[:, 0])
         for label, (m, s) in others.items():
             print(f"  {label}: predictive std on the grid " + " ".join(f"{v:.3f}" for v in s))
+    elif meth == 'hyper':
+        # a precision per layer with a Gamma(1, 1) hyper-prior, Gibbs-sampled on the device after every HMC step
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                  sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True,
+                  hyperprior=dict(a0=1.0, b0=1.0, groups='layer'))
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+        r = uqnet.mcmc_results
+        for (name, lo, hi), t in zip(r['prior_groups'], r['tau'][:, (1000 // k):].mean(axis=(0, 1))):
+            print(f"  {name} (weights {lo} .. {hi - 1}): posterior mean precision {t:.3f} (prior scale {t ** -0.5:.3f})")
     elif meth == 'nuts':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='nuts', engine='device',
@@ -173,7 +183,7 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'ess', 'nuts'):
+    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'ess', 'nuts'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]

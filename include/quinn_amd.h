@@ -420,6 +420,60 @@ int qn_sg_step(double* theta, double* v, const void* grad, int dtype, const doub
 int qn_prior_fold(const double* W, double lam, double c0, void* grad, int gdtype, double* sse, int sse_stride, int C, int64_t p,
                   void* stream);
 
+/* Hierarchical Gaussian weight prior for the device HMC / MALA engines (build-only; quinn_amd/mcmc/hyper.py restates both
+ * calls in numpy).  Groups g < G, 1 <= G <= 32, are the contiguous segments [seg[g], seg[g + 1]) of the flat weight vector
+ * (seg [G + 1] int64 ON THE DEVICE, seg[0] = 0, seg[G] = p, strictly increasing; the kernels clamp every bound to [0, p], so a
+ * wrong array gives wrong numbers, never an access outside a row), n_g entries each, and
+ *     w_j | tau_g ~ N(0, 1 / tau_g) for j in group g,     tau_g ~ Gamma(shape a0, rate b0).
+ * In the units of the sampler kernels (gs = -0.5 / sigma^2), per chain c, with S_g = sum_{j in g} w_j^2:
+ *     lam[c, g] = sigma^2 tau[c, g]
+ *     c0[c]     = sigma^2 (sum_g n_g log(2 pi / tau[c, g]) - 2 log p(tau[c, :]))
+ *     log p(tau) = sum_g (a0 log b0 - lgamma(a0) + (a0 - 1) log tau_g - b0 tau_g)
+ * so that gs (sse + sum_g lam_g S_g + c0) + (likelihood constants) is the JOINT log density of (w, tau) given the data.
+ *
+ * qn_prior_fold_g: qn_prior_fold with lam [C, G] and c0 [C] read from device arrays.  For every chain c < C, W [C, p] float64:
+ *     grad[c, j]           <- grad[c, j] + (2 lam[c, g(j)]) * W[c, j]          grad [C, p] of dtype gdtype (QN_F64 / QN_F32) or NULL
+ *     sse[c * sse_stride]  <- sse[c * sse_stride] + (sum_g lam[c, g] S_g + c0[c])      sse float64, or NULL
+ *   Arithmetic: that of qn_prior_fold -- the product (2 lam) * w, then the sum, in float64, one rounding each, no contraction; a
+ *   QN_F32 gradient is widened, updated and rounded once; same grid and element -> thread map: with all lam[c, :] equal the
+ *   gradient is qn_prior_fold's bit for bit.  The group of an element is not looked up in memory: the bounds and factors sit in
+ *   LDS and every thread walks forward through them.  S_g is summed by workgroup 0 of the chain in an order that depends on
+ *   (p, seg) alone; the terms lam_g S_g are added left to right, then c0; that workgroup is the only writer of the chain's sse
+ *   entry (the other columns of a strided sse are not touched).  No atomics, no fences: equal inputs give equal bits, a chain's
+ *   result is the same launched alone or among others, non-finite weights touch their own chain only.
+ *   QN_EINVAL with a message, before any pointer is touched: W, lam, c0 or seg NULL; grad and sse both NULL; G outside 1 .. 32;
+ *   C outside 1 .. 65535; p < 1 or p < G; sse_stride < 1 with sse given; a gdtype other than the two with grad given.
+ *
+ * qn_hyper_gibbs: one Gibbs round, launched after the accept call (and the adapt call, if any) of a step.  lam [2, C, G] and
+ *   c0 [2, C] are double-buffered by a parity of their OWN (slot hyper_parity is read, slot 1 - hyper_parity written; the caller
+ *   flips it once per round), the scalars cur_lp, best_lp [2, C] and step_ptr [2] by the step parity.  Per chain: the step t
+ *   just decided is read from slot `parity` of step_ptr; S_g is computed from cur [C, p] (the sums of qn_prior_fold_g);
+ *       tau'_g ~ Gamma(a0 + n_g / 2, rate b0 + S_g / 2),   lam'_g = sigma^2 tau'_g,   c0' as above;
+ *       taus[c, round + 1, g] = lam'_g / sigma^2           (taus [C, nrounds + 1, G] float64 or NULL; column 0 is the caller's)
+ *       grad_cur[c, j] += (2 (lam'_g(j) - lam_g(j))) * cur[c, j]
+ *       cur_lp[1 - parity, c] = cur_lp[parity, c] + gs (sum_g (lam'_g - lam_g) S_g + (c0' - c0))
+ *       best_lp[1 - parity, c] = best_lp[parity, c];   step_ptr[1 - parity] = t;   lps[c, t] = the new cur_lp (0 <= t <= nmcmc):
+ *   the stored trace is that of the state step t + 1 starts from, as after qn_pt_swap.  The caller flips both parities.
+ *   Gamma variates: Marsaglia & Tsang (2000) with the log test (no squeeze), float64 log / sqrt / cos.  Philox4x32-10 keyed
+ *   (seed, 2 t + 1, [chain0 + c : 24][11 : 4][index : 36]), index = (g << 16) | (attempt << 4) | block: block 0 of an attempt
+ *   gives the normal x = sqrt(-2 log u01(words 0, 1)) cos(2 pi u01(words 2, 3)), block 1 the uniform of the test (words 0, 1);
+ *   with d = a - 1 / 3, c = 1 / sqrt(9 d), v = (1 + c x)^3 the attempt is accepted iff v > 0 and
+ *   log u < 0.5 x^2 + d - d v + d log v, and the draw is d v / rate.  shape < 1: drawn at a = shape + 1 and multiplied by
+ *   u^(1 / shape), u = u01(words 0, 1) of index (g << 16) | (64 << 4).  The loop is BOUNDED at 64 attempts; after them the draw
+ *   is shape / rate.  A chain with a non-finite S_g (or whose new lam or c0 would not be positive / finite) keeps its tau, lam,
+ *   c0, grad_cur, cur_lp and lps[c, t] (copied to the new slots; its taus column repeats the previous one); no other chain is
+ *   touched.  Every workgroup of a chain takes the whole decision itself from the slots nobody writes in the launch: no
+ *   atomics, no fences, no arrival counters; equal inputs give equal bits and nothing depends on C or the chain's place.
+ *   QN_EINVAL with a message, before any pointer is touched: a0, b0 or sigma not > 0 or not finite; G outside 1 .. 32; C outside
+ *   1 .. 65535; p < 1 or p < G; chain0 < 0; nmcmc < 1; round outside 0 .. nrounds - 1; a parity other than 0 / 1; a NULL pointer
+ *   other than taus. */
+int qn_prior_fold_g(const double* W, const double* lam, const double* c0, const int64_t* seg, int G, void* grad, int gdtype,
+                    double* sse, int sse_stride, int C, int64_t p, void* stream);
+int qn_hyper_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* lam, double* c0,
+                   const int64_t* seg, double* taus, int64_t* step_ptr, double sigma, double a0, double b0, int G, int round,
+                   int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, int parity, int hyper_parity,
+                   void* stream);
+
 /* Elliptical slice sampling on the device (Murray, Adams & MacKay 2010; build-only, the reference has no such sampler) for
  * the target L(w) N(w; 0, priorsigma^2 I), log L = gs sse + const, gs = -0.5 / sigma^2: no step size, no warm-up, only forward
  * calls.  The chains' steps are ASYNCHRONOUS: every chain has its own step t and shrink count j, and a launch of qn_ess_iter

@@ -1,0 +1,308 @@
+// Hierarchical Gaussian weight prior for the device HMC / MALA engines (build-only: the reference has no prior in NN_MCMC):
+//   qn_prior_fold_g : qn_prior_fold with one precision per weight GROUP and per chain, read from device arrays
+//   qn_hyper_gibbs  : one exact Gibbs draw of every group's precision, and the refresh of the cached current state
+// Groups g < G <= 32 are the contiguous segments [seg[g], seg[g + 1]) of the flat weight vector, n_g entries each:
+//     w_j | tau_g ~ N(0, 1 / tau_g),   tau_g ~ Gamma(a0, rate b0),   tau_g | w ~ Gamma(a0 + n_g / 2, rate b0 + S_g / 2),
+// S_g the group's sum of squares.  In the units of the sampler kernels (gs = -0.5 / sigma^2), per chain c,
+//     lam[c, g] = sigma^2 tau[c, g],   c0[c] = sigma^2 (sum_g n_g log(2 pi / tau_g) - 2 log p(tau)),
+//     sse' = sse + (sum_g lam_g S_g + c0),      g'_j = g_j + (2 lam_g(j)) w_j
+// so gs sse' + (likelihood constants) is the JOINT log density of (w, tau) given the data, and the leapfrog, accept and adapt
+// kernels run on it untouched (quinn_amd/mcmc/hyper.py restates everything here in numpy).
+// The group of an element never comes from memory: a workgroup keeps the <= 33 segment bounds and the <= 32 factors in LDS,
+// and a thread, whose elements only ever increase, keeps the bound of its current group and that group's factor in registers
+// and walks forward when an element passes the bound.  Sums of squares: ONE workgroup sums a whole row group by group (a strided
+// loop of its 256 threads over the segment, four accumulators per thread, a fixed tree), so the order of the additions
+// depends on (p, seg) alone.  Plain vector loads and stores, no atomics, no fences, no arrival counters: whatever a launch
+// reads and writes across a chain's workgroups (lam, c0, cur_lp, best_lp, the step counter) is double-buffered by a parity.
+#include "qn_mcmc_shared.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int GMAX = 32;                  // groups at most
+constexpr int PUB = 4;                    // independent accumulators (and loads in flight) per thread of a segment's sum
+constexpr int PURPOSE_GAMMA = 11;         // Philox purpose of the Gamma variates (qn_mcmc_shared.h)
+constexpr int GAMMA_TRIES = 64;           // bound of the rejection loop
+
+struct GroupLds {
+    int64_t segs[GMAX + 1];               // the segment bounds, clamped to [0, p]
+    double fac[GMAX];                     // the per-group factor of the elementwise pass (2 lam, or 2 (lam' - lam))
+    double S[GMAX];                       // the per-group sums of squares
+    double red[GMAX * 4];                 // one partial per group and wave
+};
+
+// segment bounds -> LDS, clamped: no bound can take an index out of [0, p], whatever the array holds
+__device__ __forceinline__ void load_segs(GroupLds& l, const int64_t* __restrict__ seg, int G, int64_t p) {
+    if (threadIdx.x <= G) {
+        int64_t v = seg[threadIdx.x];
+        v = v < 0 ? 0 : (v > p ? p : v);
+        l.segs[threadIdx.x] = threadIdx.x == 0 ? 0 : (threadIdx.x == G ? p : v);
+    }
+}
+
+// l.S[g] = sum of W[j]^2 over segment g, for every g < G, by the whole workgroup (HBLK threads); l.segs must be visible.
+// Thread i adds the elements lo + i, lo + i + 256, ... into accumulator (k mod PUB) of round k; then a fixed tree.
+__device__ __forceinline__ void group_sumsq(GroupLds& l, const double* __restrict__ W, int G) {
+    for (int g = 0; g < G; ++g) {
+        const int64_t lo = l.segs[g], hi = l.segs[g + 1];
+        double acc[PUB];
+#pragma unroll
+        for (int u = 0; u < PUB; ++u) acc[u] = 0.0;
+        for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)PUB * HBLK) {
+            double wv[PUB];
+#pragma unroll
+            for (int u = 0; u < PUB; ++u) {
+                const int64_t e = e0 + (int64_t)u * HBLK;
+                wv[u] = e < hi ? W[e] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < PUB; ++u) acc[u] = acc[u] + wv[u] * wv[u];
+        }
+        double v = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if ((threadIdx.x & 63) == 0) l.red[g * 4 + (threadIdx.x >> 6)] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < G) l.S[threadIdx.x] = (l.red[threadIdx.x * 4] + l.red[threadIdx.x * 4 + 1]) +
+                                            (l.red[threadIdx.x * 4 + 2] + l.red[threadIdx.x * 4 + 3]);
+    __syncthreads();
+}
+
+// g[base + e] <- g[base + e] + fac[group of e] * W[base + e] over this workgroup's chunk of the row: the element -> thread
+// map and the arithmetic of k_prior_fold (the product, then the sum, in float64, one rounding each; TG rounded once)
+template <typename TG>
+__device__ __forceinline__ void group_axpy(const GroupLds& l, const double* __restrict__ W, TG* __restrict__ g, int G, int64_t p) {
+    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
+    int gi = 0;
+    int64_t nxt = l.segs[1];                                               // the end of the thread's current group
+    double f = l.fac[0];
+    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
+        double gv[HUB], wv[HUB];
+#pragma unroll
+        for (int u = 0; u < HUB; ++u) {
+            const int64_t e = e0 + (int64_t)u * HBLK;
+            const bool in = e < hi;
+            gv[u] = in ? (double)g[e] : 0.0;
+            wv[u] = in ? W[e] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < HUB; ++u) {
+            const int64_t e = e0 + (int64_t)u * HBLK;
+            if (e >= hi) break;
+            while (e >= nxt && gi + 1 < G) {                                // (elements only increase: a forward walk in LDS)
+                ++gi;
+                nxt = l.segs[gi + 1];
+                f = l.fac[gi];
+            }
+            const double t = f * wv[u];                                     // (two roundings: the product, then the sum)
+            g[e] = (TG)(gv[u] + t);
+        }
+    }
+}
+
+template <typename TG>
+__global__ __launch_bounds__(HBLK) void k_prior_fold_g(const double* __restrict__ W, const double* __restrict__ lam,
+                                                       const double* __restrict__ c0, const int64_t* __restrict__ seg, int G,
+                                                       TG* __restrict__ g, double* __restrict__ sse, int sse_stride, int64_t p) {
+    __shared__ GroupLds l;
+    const int b = blockIdx.y;
+    const int64_t base = (int64_t)b * p;
+    load_segs(l, seg, G, p);
+    if (threadIdx.x < G) l.fac[threadIdx.x] = 2.0 * lam[(int64_t)b * G + threadIdx.x];
+    __syncthreads();
+    if (g) group_axpy<TG>(l, W + base, g + base, G, p);
+    if (!sse || blockIdx.x != 0) return;                                   // (uniform over the workgroup)
+    group_sumsq(l, W + base, G);
+    if (threadIdx.x == 0) {
+        double term = lam[(int64_t)b * G] * l.S[0];
+        for (int k = 1; k < G; ++k) term = term + lam[(int64_t)b * G + k] * l.S[k];
+        double* out = sse + (int64_t)b * sse_stride;
+        term = term + c0[b];
+        *out = *out + term;
+    }
+}
+
+// ---- Gamma(shape, rate) by Marsaglia & Tsang (2000), the log test only (no squeeze), at most GAMMA_TRIES attempts.
+// Attempt k of group g reads two Philox blocks, index (g << 16) | (k << 4) | block: block 0 gives the normal (Box-Muller in
+// float64 on u01(words 0, 1), u01(words 2, 3)), block 1 the uniform of the test (words 0, 1).  shape < 1: the draw at shape + 1
+// times u^(1 / shape), u from words 0, 1 of index (g << 16) | (GAMMA_TRIES << 4).  No attempt accepted: shape / rate.
+__device__ double gamma_draw(uint64_t seed, uint64_t stream, int chain, int g, double shape, double rate) {
+    const double a = shape < 1.0 ? shape + 1.0 : shape;
+    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    Philox ph;
+    for (int k = 0; k < GAMMA_TRIES; ++k) {
+        ph.gen(seed, stream, ctr_of(chain, PURPOSE_GAMMA, ((uint64_t)g << 16) | ((uint64_t)k << 4)));
+        const double u1 = u01(ph.c[0], ph.c[1]), u2 = u01(ph.c[2], ph.c[3]);
+        const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        const double t = 1.0 + c * x;
+        if (!(t > 0.0)) continue;
+        const double v = t * t * t;
+        ph.gen(seed, stream, ctr_of(chain, PURPOSE_GAMMA, ((uint64_t)g << 16) | ((uint64_t)k << 4) | 1));
+        const double u = u01(ph.c[0], ph.c[1]);
+        if (log(u) < 0.5 * x * x + d - d * v + d * log(v)) {
+            double gam = d * v;
+            if (shape < 1.0) {
+                ph.gen(seed, stream, ctr_of(chain, PURPOSE_GAMMA, ((uint64_t)g << 16) | ((uint64_t)GAMMA_TRIES << 4)));
+                gam = gam * exp(log(u01(ph.c[0], ph.c[1])) / shape);
+            }
+            return gam / rate;
+        }
+    }
+    return shape / rate;
+}
+
+struct GibbsArgs {
+    int G, round, nrounds, C, chain0, nmcmc, par, hpar;
+    int64_t p;
+    uint64_t seed;
+    double sigma, a0, b0, kconst;         // kconst = a0 log b0 - lgamma(a0), the constant of one log p(tau_g)
+};
+
+// Every workgroup of a chain takes the whole decision itself -- the sums of squares of the chain's row and the G draws, from
+// slot `hpar` of lam / c0 and slot `par` of the scalars, which nobody writes in this launch -- then refreshes its own chunk of
+// the cached gradient; workgroup 0 writes the other slots.
+__global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double* __restrict__ cur, double* __restrict__ gcur,
+                                                      double* cur_lp, double* best_lp, double* __restrict__ lps, double* lam,
+                                                      double* c0, const int64_t* __restrict__ seg, double* __restrict__ taus,
+                                                      int64_t* step_ptr) {
+    __shared__ GroupLds l;
+    __shared__ double lamo[GMAX], lamn[GMAX], term[GMAX];
+    const int b = blockIdx.y, G = a.G;
+    const int64_t base = (int64_t)b * a.p;
+    const int64_t t = step_ptr[a.par];
+    const double* lo_ = lam + ((int64_t)a.hpar * a.C + b) * G;
+    load_segs(l, seg, G, a.p);
+    if (threadIdx.x < G) lamo[threadIdx.x] = lo_[threadIdx.x];
+    __syncthreads();
+    group_sumsq(l, cur + base, G);
+    const double s2 = a.sigma * a.sigma;
+    if (threadIdx.x < G) {
+        const int g = threadIdx.x;
+        const double n = (double)(l.segs[g + 1] - l.segs[g]), S = l.S[g];
+        double tau = NAN;
+        if (fabs(S) < INFINITY)                                                // (finite; a sum of squares is never negative)
+            tau = gamma_draw(a.seed, 2 * (uint64_t)t + 1, a.chain0 + b, g, a.a0 + 0.5 * n, a.b0 + 0.5 * S);
+        const double ln = s2 * tau;
+        lamn[g] = ln;
+        l.fac[g] = 2.0 * (ln - lamo[g]);
+        // this group's part of c0 / sigma^2: n_g log(2 pi / tau_g) - 2 log p(tau_g)
+        const double lt = log(tau);
+        term[g] = n * log(6.283185307179586 / tau) - 2.0 * (a.kconst + (a.a0 - 1.0) * lt - a.b0 * tau);
+    }
+    __syncthreads();
+    bool ok = true;                       // every new precision positive and finite, in lam's units too, and its term finite
+    for (int g = 0; g < G; ++g) ok = ok && lamn[g] > 0.0 && lamn[g] < INFINITY && fabs(term[g]) < INFINITY;
+    if (ok) group_axpy<double>(l, cur + base, gcur + base, G, a.p);
+    if (blockIdx.x != 0) return;
+    double* ln_ = lam + ((int64_t)(1 - a.hpar) * a.C + b) * G;
+    if (threadIdx.x < G) {
+        const int g = threadIdx.x;
+        ln_[g] = ok ? lamn[g] : lamo[g];
+        if (taus) {
+            double* row = taus + ((int64_t)b * (a.nrounds + 1) + a.round) * G;
+            row[G + g] = ok ? lamn[g] / s2 : row[g];                            // (a frozen chain repeats its last column)
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int so = a.par * a.C, sn = (1 - a.par) * a.C;
+        const double c0o = c0[a.hpar * a.C + b], clp = cur_lp[so + b];
+        double nlp = clp, c0n = c0o;
+        if (ok) {
+            double dsum = (lamn[0] - lamo[0]) * l.S[0], tsum = term[0];
+            for (int g = 1; g < G; ++g) {
+                dsum = dsum + (lamn[g] - lamo[g]) * l.S[g];
+                tsum = tsum + term[g];
+            }
+            c0n = s2 * tsum;
+            nlp = clp + (-0.5 / s2) * (dsum + (c0n - c0o));
+        }
+        c0[(1 - a.hpar) * a.C + b] = c0n;
+        cur_lp[sn + b] = nlp;
+        best_lp[sn + b] = best_lp[so + b];
+        // the stored trace is that of the state step t + 1 starts from (the convention of qn_pt_swap)
+        if (ok && t >= 0 && t <= a.nmcmc) lps[(int64_t)b * (a.nmcmc + 1) + t] = nlp;
+        if (b == 0) step_ptr[1 - a.par] = t;                                   // no step was taken: the caller only flips its parity
+    }
+}
+
+}  // namespace
+
+extern "C" int qn_prior_fold_g(const double* W, const double* lam, const double* c0, const int64_t* seg, int G, void* grad,
+                               int gdtype, double* sse, int sse_stride, int C, int64_t p, void* stream) {
+    if (!W || !lam || !c0 || !seg) {
+        qn_set_error("qn_prior_fold_g: W, lam, c0 or seg is NULL");
+        return QN_EINVAL;
+    }
+    if (!grad && !sse) {
+        qn_set_error("qn_prior_fold_g: grad and sse are both NULL (nothing to fold the prior into)");
+        return QN_EINVAL;
+    }
+    if (G < 1 || G > GMAX) {
+        qn_set_error("qn_prior_fold_g: G = %d groups, 1 <= G <= %d", G, GMAX);
+        return QN_EINVAL;
+    }
+    if (C < 1 || C > 65535 || p < 1 || p < G) {
+        qn_set_error("qn_prior_fold_g: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d))", C, (long long)p, G);
+        return QN_EINVAL;
+    }
+    if (sse && sse_stride < 1) {
+        qn_set_error("qn_prior_fold_g: sse_stride = %d must be >= 1", sse_stride);
+        return QN_EINVAL;
+    }
+    if (grad && gdtype != QN_F64 && gdtype != QN_F32) {
+        qn_set_error("qn_prior_fold_g: gdtype = %d is neither QN_F64 nor QN_F32", gdtype);
+        return QN_EINVAL;
+    }
+    const dim3 grid(grad ? hmc_parts(p) : 1, C), blk(HBLK);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    if (grad && gdtype == QN_F32)
+        hipLaunchKernelGGL(k_prior_fold_g<float>, grid, blk, 0, st, W, lam, c0, seg, G, static_cast<float*>(grad), sse, sse_stride, p);
+    else
+        hipLaunchKernelGGL(k_prior_fold_g<double>, grid, blk, 0, st, W, lam, c0, seg, G, static_cast<double*>(grad), sse, sse_stride, p);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}
+
+extern "C" int qn_hyper_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* lam,
+                              double* c0, const int64_t* seg, double* taus, int64_t* step_ptr, double sigma, double a0,
+                              double b0, int G, int round, int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed,
+                              int parity, int hyper_parity, void* stream) {
+    if (!(a0 > 0.0) || !std::isfinite(a0) || !(b0 > 0.0) || !std::isfinite(b0) || !(sigma > 0.0) || !std::isfinite(sigma)) {
+        qn_set_error("qn_hyper_gibbs: a0 = %g, b0 = %g and sigma = %g must be > 0 and finite", a0, b0, sigma);
+        return QN_EINVAL;
+    }
+    if (G < 1 || G > GMAX) {
+        qn_set_error("qn_hyper_gibbs: G = %d groups, 1 <= G <= %d", G, GMAX);
+        return QN_EINVAL;
+    }
+    if (C < 1 || C > 65535 || p < 1 || p < G || chain0 < 0 || nmcmc < 1) {
+        qn_set_error("qn_hyper_gibbs: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d), chain0 = %d >= 0, nmcmc = %d >= 1)",
+                     C, (long long)p, G, chain0, nmcmc);
+        return QN_EINVAL;
+    }
+    if (nrounds < 1 || round < 0 || round >= nrounds) {
+        qn_set_error("qn_hyper_gibbs: round = %d outside 0 .. nrounds - 1 = %d", round, nrounds - 1);
+        return QN_EINVAL;
+    }
+    if ((parity != 0 && parity != 1) || (hyper_parity != 0 && hyper_parity != 1)) {
+        qn_set_error("qn_hyper_gibbs: parity = %d and hyper_parity = %d are 0 or 1", parity, hyper_parity);
+        return QN_EINVAL;
+    }
+    if (!cur || !grad_cur || !cur_lp || !best_lp || !lps || !lam || !c0 || !seg || !step_ptr) {
+        qn_set_error("qn_hyper_gibbs: a required pointer is NULL (only taus is optional)");
+        return QN_EINVAL;
+    }
+    GibbsArgs a;
+    a.G = G; a.round = round; a.nrounds = nrounds; a.C = C; a.chain0 = chain0; a.nmcmc = nmcmc; a.par = parity; a.hpar = hyper_parity;
+    a.p = p; a.seed = seed; a.sigma = sigma; a.a0 = a0; a.b0 = b0;
+    a.kconst = a0 * std::log(b0) - std::lgamma(a0);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_hyper_gibbs, dim3(hmc_parts(p), C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), a, cur, grad_cur,
+                       cur_lp, best_lp, lps, lam, c0, seg, taus, step_ptr);
+    QN_HIP_CHECK(hipGetLastError());
+    return QN_OK;
+}

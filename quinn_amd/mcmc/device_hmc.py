@@ -38,12 +38,23 @@ ladder = None (default) runs exactly what ran before, through the same entry poi
 the initial and every leapfrog gradient call adds lam |q|^2 + c0 to the SSE and 2 lam q to the gradient (q: the float64 positions),
 and everything above -- forces, accept test, warm-up, ladder, graph, groups -- runs on the posterior with the prior, untouched.
 priorsigma = None (default) makes no such launch.
+
+`hyperprior` = dict(a0=, b0=, groups='layer' | 'tensor' | 'all', every=1, tau0=None) replaces the one scalar by a precision per
+weight group and chain with a Gamma(a0, rate b0) hyper-prior (`quinn_amd.mcmc.hyper` states the contract): the run state gains
+the device arrays s['lam'] [2, C, G], s['c0'] [2, C] (double-buffered by the parity s['hpar'] of their own), s['seg'] [G + 1] and
+s['taus'] [C, nrounds + 1, G]; while s['lam'] is set, qn_prior_fold_g stands where qn_prior_fold stood, and every `every`-th
+step, warm-up included, is followed by one qn_hyper_gibbs launch (order within a step: accept, adapt, Gibbs round) that draws
+the precisions and refreshes the cached gradient and log density of the current state.  'logpost' / 'maxpost' are then the JOINT
+log density of (w, tau); the results gain 'tau' [C, nrounds + 1, G] (column 0: the initial precisions, tau0, else
+1 / priorsigma^2, else a0 / b0) and the engine the attribute `prior_groups` [(name, lo, hi)].  every = 0 never draws (fixed
+per-group scales from tau0).  Not with a ladder or a graph.  hyperprior = None (default) makes exactly the launches made before.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from .adapt import TARGET_ACCEPT, check_adapt_args, warmup_plan
+from .hyper import check_hyperprior, check_segments, fold_constants_g, group_segments, initial_tau
 from .tempering import check_temper_args, check_whole_ladders
 from .device_engine import DeviceEngine
 
@@ -56,7 +67,7 @@ class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
     def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
-                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None):
+                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None):
         # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
         # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
         # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
@@ -73,6 +84,18 @@ class DeviceHMC(DeviceEngine):
         self.beta_min, self.swap_every = float(beta_min), swap_every
         self._ladder = None if ladder is None else check_temper_args(ladder, beta_min, swap_every, chain0=self.chain0,
                                                                      use_graph=self.use_graph)
+        # hierarchical prior: the settings (None: the scalar prior or none) and the weight groups, known before any launch
+        self._hyper = check_hyperprior(hyperprior)
+        self.prior_groups = None
+        if self._hyper is not None:
+            if self._ladder is not None:
+                raise ValueError("hyperprior does not run with a ladder (a tempered rung would need its own precisions)")
+            if self.use_graph:
+                raise ValueError("hyperprior does not run with use_graph=True (the round counter changes from launch to launch)")
+            seg, names = group_segments(op.arch, self._hyper['groups'])
+            self._seg = check_segments(seg, op.p)
+            initial_tau(self._hyper, len(names), self.priorsigma)              # (a tau0 of the wrong length is refused here)
+            self.prior_groups = [(n, int(lo), int(hi)) for n, lo, hi in zip(names, seg[:-1], seg[1:])]
 
     def _begin(self, s, st):
         """Enqueue the begin call of a step.  The entry point follows from what the state holds: s['beta'] (a ladder) -> _t,
@@ -109,7 +132,9 @@ class DeviceHMC(DeviceEngine):
         for j in range(self.L):
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
-            if self._prior is not None:                                       # (the float64 positions, also under a float32 operator)
+            if s.get('lam') is not None:                                      # per-group precisions: the current slot of lam / c0
+                self.op.prior_fold_g(s['q'], s['lam'][s['hpar']], s['c0'][s['hpar']], s['seg'], sse=s['sse'], grad=s['gq'])
+            elif self._prior is not None:                                     # (the float64 positions, also under a float32 operator)
                 self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
             self._leap(s, j == self.L - 1, st)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
@@ -137,6 +162,16 @@ class DeviceHMC(DeviceEngine):
         s['par'] ^= 1
         s['round'] += 1
 
+    def _hyper_step(self, s, nmcmc):
+        """Enqueue Gibbs round s['hround'] of the group precisions after the step just decided (and its adaptation): like
+        `_swap_step` it reads slot s['par'] of the scalars and writes the other, and slot s['hpar'] of lam / c0 likewise."""
+        a0, b0 = s['hyper']
+        self.op.hyper_gibbs(s['cur'], s['gcur'], s['cur_lp'], s['best_lp'], s['lps'], s['lam'], s['c0'], s['seg'], s['taus'],
+                            s['step'], self.sigma, a0, b0, s['hround'], self.chain0, self.seed, s['par'], s['hpar'])
+        s['par'] ^= 1
+        s['hpar'] ^= 1
+        s['hround'] += 1
+
     def _adapt_step(self, s, nmcmc, a):
         """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
         from the slot of the step counter the accept call wrote, which is s['par'] after `_step`."""
@@ -154,7 +189,8 @@ class DeviceHMC(DeviceEngine):
     def _clone(self, op, chain0):
         return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
                          target_accept=self.target_accept, adapt_mass=self.adapt_mass, ladder=self._ladder,
-                         beta_min=self.beta_min, swap_every=self.swap_every, priorsigma=self.priorsigma)
+                         beta_min=self.beta_min, swap_every=self.swap_every, priorsigma=self.priorsigma,
+                         hyperprior=self._hyper)
 
     def _check_groups(self, nmcmc, C, p):
         if self._ladder is not None:
@@ -170,6 +206,8 @@ class DeviceHMC(DeviceEngine):
         if self._ladder is not None:
             for k in ('beta', 'swap_rate', 'replica'):
                 out[k] = torch.cat([r[k] for r in res])
+        if self._hyper is not None:
+            out['tau'] = torch.cat([r['tau'] for r in res])
 
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
@@ -182,9 +220,24 @@ class DeviceHMC(DeviceEngine):
         nk = int(self._L.qn_hmc_parts(p))
         f32op = self.op.tdt != f64
         sse0, g0 = self.op.sse_grad(cur if not f32op else cur.to(self.op.tdt))
-        if self._prior is not None:
+        hs = None
+        if self._hyper is not None:
+            # per chain and group: lam = sigma^2 tau and the constant c0, double-buffered; the trace of the precisions
+            hp, G = self._hyper, len(self._seg) - 1
+            every = hp['every']
+            tau = np.tile(initial_tau(hp, G, self.priorsigma), (C, 1))
+            lam, c0 = fold_constants_g(self.sigma, tau, self._seg, hp['a0'], hp['b0'])
+            lam, c0 = torch.as_tensor(lam, dtype=f64, device=dev), torch.as_tensor(c0, dtype=f64, device=dev)
+            hs = {'lam': torch.stack([lam, lam]), 'c0': torch.stack([c0, c0]), 'seg': torch.as_tensor(self._seg, device=dev),
+                  'taus': torch.empty(C, (nmcmc // every if every else 0) + 1, G, dtype=f64, device=dev), 'hpar': 0, 'hround': 0,
+                  'hyper': (hp['a0'], hp['b0']), 'nstep': 0}
+            hs['taus'][:, 0] = torch.as_tensor(tau, dtype=f64, device=dev)
+            self.op.prior_fold_g(cur, hs['lam'][0], hs['c0'][0], hs['seg'], sse=sse0, grad=g0)
+        elif self._prior is not None:
             self.op.prior_fold(cur, *self._prior, sse=sse0, grad=g0)
         s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
+        if hs is not None:
+            s.update(hs)
         s.update({'gcur': g0.double() if f32op else g0.clone(),
                   'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),
                   'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
@@ -217,6 +270,17 @@ class DeviceHMC(DeviceEngine):
                 s['nstep'] = s.get('nstep', 0) + 1
                 if s['nstep'] % int(self.swap_every) == 0:
                     self._swap_step(s, nmcmc)
+        elif hs is not None and self._hyper['every']:
+            plain = self._step
+
+            def step(s, nmcmc, a=None):
+                """accept, adapt, Gibbs round: the launch order of a step under a hyper-prior."""
+                plain(s, nmcmc)
+                if a is not None:
+                    self._adapt_step(s, nmcmc, a)
+                s['nstep'] += 1
+                if s['nstep'] % self._hyper['every'] == 0:
+                    self._hyper_step(s, nmcmc)
         if self.adapt:
             # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
             plan = warmup_plan(self.adapt, self.adapt_mass)
@@ -230,7 +294,7 @@ class DeviceHMC(DeviceEngine):
             s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             for a in plan:
-                if self._ladder is None:
+                if step == self._step:
                     step(s, nmcmc)
                     self._adapt_step(s, nmcmc, a)
                 else:
@@ -270,4 +334,6 @@ class DeviceHMC(DeviceEngine):
             out.update(epsilon=s['eps'], mass_scale=s['scale'], nwarm=self.adapt)
         if self._ladder is not None:
             out.update(beta=s['beta'], swap_rate=s['swap_acc'].double() / s['swap_try'].double(), replica=s['rep'])
+        if hs is not None:
+            out['tau'] = s['taus']
         return out

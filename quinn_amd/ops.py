@@ -460,6 +460,75 @@ class BatchedMLP:
             _lib.check(self._L.qn_prior_fold(W.data_ptr(), float(lam), float(c0), _ptr(grad), gdt, _ptr(sse), int(sse_stride),
                                              C, p, _lib.stream(self.device)), "qn_prior_fold")
 
+    def _check_groups(self, what, lam, c0, seg, C, lead=()):
+        """lam [*lead, C, G], c0 [*lead, C] float64 and seg [G + 1] int64, contiguous device tensors; returns G."""
+        if not isinstance(seg, torch.Tensor) or seg.dtype != torch.int64 or seg.dim() != 1 or not seg.is_contiguous() or \
+                not seg.is_cuda or not 2 <= seg.numel() <= 33:
+            raise ValueError(f"{what}: seg is a contiguous int64 device tensor [G + 1], 1 <= G <= 32")
+        G = seg.numel() - 1
+        for t, shape, name in ((lam, lead + (C, G), "lam"), (c0, lead + (C,), "c0")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                    not t.is_cuda:
+                raise ValueError(f"{what}: {name} is a contiguous float64 device tensor {list(shape)}")
+        return G
+
+    def prior_fold_g(self, W, lam, c0, seg, sse=None, grad=None, sse_stride=1):
+        """`prior_fold` with one precision per weight group and chain, read from device tensors (qn_prior_fold_g, one launch on
+        the current stream, in place): grad [C, p] += (2 lam[c, g(j)]) W, sse[c * sse_stride] += sum_g lam[c, g] S_g + c0[c].
+        lam [C, G], c0 [C] float64; seg [G + 1] int64, the group bounds (`quinn_amd.mcmc.hyper.fold_constants_g`,
+        `group_segments`)."""
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
+            raise ValueError("prior_fold_g: W is a contiguous float64 device tensor [C, p]")
+        C, p = W.shape
+        G = self._check_groups("prior_fold_g", lam, c0, seg, C)
+        gdt = _lib.QN_F64
+        if grad is not None:
+            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
+                raise ValueError("prior_fold_g: grad is a contiguous float64 / float32 tensor of W's shape")
+            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
+        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
+                                sse.numel() != C * int(sse_stride)):
+            raise ValueError("prior_fold_g: sse is a contiguous float64 tensor of C * sse_stride entries")
+        if C == 0:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_prior_fold_g(W.data_ptr(), lam.data_ptr(), c0.data_ptr(), seg.data_ptr(), G, _ptr(grad), gdt,
+                                               _ptr(sse), int(sse_stride), C, p, _lib.stream(self.device)), "qn_prior_fold_g")
+
+    def hyper_gibbs(self, cur, grad_cur, cur_lp, best_lp, lps, lam, c0, seg, taus, step, sigma, a0, b0, round, chain0, seed,
+                    parity, hyper_parity):
+        """One Gibbs round of the group precisions after the step just decided (qn_hyper_gibbs, one launch on the current
+        stream; `quinn_amd.mcmc.hyper.gibbs_round` restates it): cur, grad_cur [C, p], cur_lp, best_lp [2, C], lps
+        [C, nmcmc + 1], lam [2, C, G], c0 [2, C] float64; seg [G + 1], step [2] int64; taus [C, nrounds + 1, G] float64 or
+        None.  Slot `parity` of the scalars and slot `hyper_parity` of lam / c0 are read, the other slots written: the caller
+        flips both."""
+        if not isinstance(cur, torch.Tensor) or cur.dtype != torch.float64 or cur.dim() != 2 or not cur.is_contiguous() or \
+                not cur.is_cuda:
+            raise ValueError("hyper_gibbs: cur is a contiguous float64 device tensor [C, p]")
+        C, p = cur.shape
+        G = self._check_groups("hyper_gibbs", lam, c0, seg, C, lead=(2,))
+        for t, shape, name in ((grad_cur, (C, p), "grad_cur"), (cur_lp, (2, C), "cur_lp"), (best_lp, (2, C), "best_lp")):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"hyper_gibbs: {name} is a contiguous float64 device tensor {list(shape)}")
+        if lps.dtype != torch.float64 or lps.dim() != 2 or lps.shape[0] != C or lps.shape[1] < 2 or not lps.is_contiguous():
+            raise ValueError("hyper_gibbs: lps is a contiguous float64 tensor [C, nmcmc + 1], nmcmc >= 1")
+        if step.dtype != torch.int64 or step.numel() != 2 or not step.is_contiguous():
+            raise ValueError("hyper_gibbs: step is the double-buffered int64 step counter [2]")
+        nrounds = int(round) + 1
+        if taus is not None:
+            if taus.dtype != torch.float64 or taus.dim() != 3 or taus.shape[0] != C or taus.shape[2] != G or \
+                    taus.shape[1] < 2 or not taus.is_contiguous():
+                raise ValueError("hyper_gibbs: taus is a contiguous float64 tensor [C, nrounds + 1, G], nrounds >= 1")
+            nrounds = taus.shape[1] - 1
+        if C == 0:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_hyper_gibbs(cur.data_ptr(), grad_cur.data_ptr(), cur_lp.data_ptr(), best_lp.data_ptr(),
+                                              lps.data_ptr(), lam.data_ptr(), c0.data_ptr(), seg.data_ptr(), _ptr(taus),
+                                              step.data_ptr(), float(sigma), float(a0), float(b0), G, int(round), nrounds, C,
+                                              int(chain0), p, lps.shape[1] - 1, int(seed), int(parity), int(hyper_parity),
+                                              _lib.stream(self.device)), "qn_hyper_gibbs")
+
     def sse_pred(self, W, row_idx=None):
         s, pr, _ = self._call(W, row_idx, True, False)
         return s, pr

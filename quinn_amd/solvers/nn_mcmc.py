@@ -32,6 +32,7 @@ from ..mcmc.nuts import check_nuts_args
 from ..mcmc import diagnostics as diag
 from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
+from ..mcmc.hyper import check_hyperprior, group_segments, initial_tau
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
@@ -148,7 +149,7 @@ class NN_MCMC(QUiNNBase):
     # -- fit -------------------------------------------------------------------------------
     def fit(self, xtrn, ytrn, zflag=True, datanoise=0.05, nmcmc=6000, param_ini=None, sampler='amcmc',
             sampler_params=None, *, nchains=1, seeds=None, engine='host', gather='all', gather_chain=None, bfgs_jac=None,
-            diagnostics=False, diag_nburn=None, gtrn=None, gradnoise=None, priorsigma=None):
+            diagnostics=False, diag_nburn=None, gtrn=None, gradnoise=None, priorsigma=None, hyperprior=None):
         """Run MCMC over the flat weight vector.
 
         Args (reference): xtrn `(N,d)`, ytrn `(N,o)`, zflag (BFGS pre-fit of a random start),
@@ -226,9 +227,36 @@ class NN_MCMC(QUiNNBase):
             tempers likelihood and prior alike: a hot rung's prior has variance s^2 / beta).  The SG samplers' prior is
             exact, only their likelihood is a minibatch estimate.  One scalar s: no per-layer or ARD scales, no hyper-prior.
             Anything but None or a finite s > 0 raises ValueError before any launch.
+
+            hyperprior: None (default; exactly the launches made without the argument) or dict(a0=, b0=, groups='layer' |
+            'tensor' | 'all', every=1, tau0=None) -- the hierarchical prior of `quinn_amd.mcmc.hyper`: a zero-mean Gaussian
+            per weight group ('layer': each Linear's weight and bias; 'tensor': every parameter tensor; 'all': one group; at
+            most 32) whose precision tau_g ~ Gamma(shape a0, rate b0) is Gibbs-sampled on the device after every `every`-th
+            step, per chain.  Initial precisions: tau0 (a scalar or one per group), else 1 / priorsigma^2, else a0 / b0.
+            every=0 never draws: fixed per-group scales from tau0 (required then).  sampler='hmc' | 'mala' with
+            engine='device' only (with adapt, groups, gather_chain, diagnostics, predict_ens, score and rank sharding); not
+            with a ladder, use_graph=True or a residual network: ValueError.  'logpost' / 'maxpost' and the MAP bookkeeping are
+            then those of the JOINT density of (w, tau) (`hyper.log_joint`), a function of the chain's whole state, so the
+            R-hat of its trace means something; a joint mode in tau is of limited use -- predict with `predict_ens` /
+            `score`, not from the MAP.  mcmc_results gains 'tau' [C, nrounds + 1, G] (the precisions after every round; column
+            0 the initial ones) and 'prior_groups' [(name, lo, hi)]; the settings are stored in lpinfo['lparams']['hyperprior'].
         """
         self.diagnostics = None
         priorsigma = check_priorsigma(priorsigma)
+        hyperprior = check_hyperprior(hyperprior)
+        if hyperprior is not None:                # (before any device is touched)
+            sp = dict(sampler_params or {})
+            if sampler not in ('hmc', 'mala') or engine != 'device':
+                raise ValueError(f"hyperprior runs with sampler='hmc' | 'mala' and engine='device' only (got sampler={sampler!r}, "
+                                 f"engine={engine!r})")
+            if sp.get('ladder') is not None:
+                raise ValueError("hyperprior does not run with a ladder (a tempered rung would need its own precisions)")
+            if sp.get('use_graph'):
+                raise ValueError("hyperprior does not run with use_graph=True (the round counter changes from launch to launch)")
+            if type(self.arch).__name__ != 'MLPArch':
+                raise ValueError("hyperprior: weight groups are defined for plain MLPs, not for a residual network (RNet)")
+            hseg, hnames = group_segments(self.arch, hyperprior['groups'])
+            initial_tau(hyperprior, len(hnames), priorsigma)
         if sampler in DEVICE_ONLY and engine != 'device':
             raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host engine for it)")
         if sampler == 'ess':                     # (before any device is touched)
@@ -248,6 +276,8 @@ class NN_MCMC(QUiNNBase):
                        'lparams': {'sigma': datanoise}}
         if priorsigma is not None:
             self.lpinfo['lparams']['priorsigma'] = priorsigma
+        if hyperprior is not None:
+            self.lpinfo['lparams']['hyperprior'] = hyperprior
         if gtrn is not None:
             if engine == 'device':
                 raise NotImplementedError("gradient observations (gtrn) need engine='host': the device samplers' accept "
@@ -309,6 +339,8 @@ class NN_MCMC(QUiNNBase):
                 for k in ('epsilon', 'mass_scale'):
                     if np.ndim(sampler_params.get(k)) >= 1:
                         sampler_params[k] = np.asarray(sampler_params[k], dtype=np.float64)[lo:hi]
+            if hyperprior is not None:
+                sampler_params['hyperprior'] = hyperprior
             eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, priorsigma=priorsigma, **sampler_params)
             if hi > lo:
                 res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
@@ -320,6 +352,9 @@ class NN_MCMC(QUiNNBase):
             else:
                 res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)),
                                     nrounds=nrounds)
+                if hyperprior is not None:
+                    nr = nmcmc // hyperprior['every'] if hyperprior['every'] else 0
+                    res['tau'] = np.zeros((0, nr + 1, len(hnames)))
                 if sampler == 'ess':
                     res.update(nev=np.zeros((0, nmcmc + 1), dtype=np.int32), ntrunc=np.zeros(0, dtype=np.int64),
                                nevals=np.zeros(0, dtype=np.int64))
@@ -338,6 +373,8 @@ class NN_MCMC(QUiNNBase):
             self.mcmc_results = res
             if np.ndim(param_ini) == 1:
                 self.mcmc_results = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in self.mcmc_results.items()}
+            if hyperprior is not None:
+                self.mcmc_results['prior_groups'] = [(n, int(a), int(b)) for n, a, b in zip(hnames, hseg[:-1], hseg[1:])]
             self.samples, self.cmode = self.mcmc_results['chain'], self.mcmc_results['mapparams']
             return
         if sampler == 'amcmc':
