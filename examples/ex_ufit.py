@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -50,7 +50,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -59,7 +59,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'hyper', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -121,6 +121,22 @@ def main(meth, quick=False, mlp=False):
         r = uqnet.mcmc_results
         for (name, lo, hi), t in zip(r['prior_groups'], r['tau'][:, (1000 // k):].mean(axis=(0, 1))):
             print(f"  {name} (weights {lo} .. {hi - 1}): posterior mean precision {t:.3f} (prior scale {t ** -0.5:.3f})")
+    elif meth == 'noise':
+        # no hand-set scale.  Gibbs-sampling the noise from a random start finds the 'everything is noise' mode (a large SSE draws
+        # a large noise level, at which the weights barely move), so a first run at a fixed, ten times too large noise level
+        # brings the chains to the data; the second starts where it ended and samples the noise level after every HMC step
+        # (the weight scale per layer likewise, in both runs)
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        common = dict(zflag=False, datanoise=10 * datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                      sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), hyperprior=dict(a0=1.0, b0=1.0, groups='layer'))
+        uqnet.fit(xtrn, ytrn, **common)
+        uqnet.fit(xtrn, ytrn, param_ini=uqnet.samples[:, -1], diagnostics=True, noiseprior=dict(a0=2.0, b0=1e-3), **common)
+        predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+        sig = uqnet.mcmc_results['sigma'][:, (1000 // k):]
+        print(f"  noise level: started at {10 * datanoise:g}, posterior mean {sig.mean():.4f} "
+              f"(5 % .. 95 %: {np.quantile(sig, 0.05):.4f} .. {np.quantile(sig, 0.95):.4f}); the data's is {datanoise:g}")
+        sc = uqnet.score(xtst, ytst, nsam=100 // k * 2, nburn=1000 // k, chain='all')
+        print(f"  test nlpd at the sampled levels {sc['nlpd']:.3f}, 90 % coverage {sc['coverage'][0.9]:.2f}")
     elif meth == 'nuts':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='nuts', engine='device',
@@ -183,7 +199,7 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'ess', 'nuts'):
+    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]

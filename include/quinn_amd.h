@@ -474,6 +474,67 @@ int qn_hyper_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* 
                    int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, int parity, int hyper_parity,
                    void* stream);
 
+/* Conjugate hyper-prior on the noise level of the Gaussian likelihood for the device HMC / MALA engines (build-only;
+ * quinn_amd/mcmc/noise.py restates both calls in numpy).  One noise variance s2_c per chain, shared by all n = N * o entries
+ * of y (N rows, o outputs):
+ *     y_k | w, s2 ~ N(M_w(x)_k, s2),     1 / s2 ~ Gamma(shape a0, rate b0),
+ *     1 / s2 | w, y ~ Gamma(a0 + n / 2, rate b0 + SSE(w) / 2)          (SSE: the data sum of squares alone, without a prior).
+ * The weight prior is NOT scaled by s2.  Every sampler kernel keeps the nominal noise level sigma0 it is called with
+ * (gs = -h, h = 0.5 / sigma0^2, and the accept kernel's lik_const = (N / 2) log 2 pi + N log sigma0); per chain c
+ *     kappa[c] = sigma0^2 / s2_c
+ *     d0[c]    = sigma0^2 (n log(2 pi s2_c) - 2 log p(s2_c) - N log(2 pi sigma0^2))
+ *     log p(s2) = a0 log b0 - lgamma(a0) + (a0 + 1) log(1 / s2) - b0 / s2           (the density of s2, Jacobian included)
+ * so that -(h sse' + lik_const) with sse' = kappa sse + P + d0, P = sum_g lam_g S_g + c0 the weight prior's term in the units
+ * of qn_prior_fold_g (absent without a prior), is the JOINT log density of (w, s2[, tau]) given the data; the normaliser covers
+ * all N * o entries (the kernels' constant counts N, d0 removes it).  At fixed s2 the accept ratio is the conditional's.
+ *
+ * qn_noise_fold: the fold above in ONE launch; it stands where qn_prior_fold / qn_prior_fold_g stand.  For every chain c < C,
+ *   W [C, p] float64, kappa [C], d0 [C] float64 on the device, and the weight prior as lam [C, G], c0 [C], seg [G + 1] of
+ *   qn_prior_fold_g with 0 <= G <= 32 (G = 0: no weight prior, the three pointers are not read; a scalar prior is G = 1):
+ *     grad[c, j]           <- kappa[c] * grad[c, j] + (2 lam[c, g(j)]) * W[c, j]     grad [C, p] of dtype gdtype (QN_F64 / QN_F32) or NULL
+ *     sse[c * sse_stride]  <- (kappa[c] * sse[c * sse_stride] + P) + d0[c]           sse float64, or NULL
+ *   Arithmetic: float64, no contraction, one rounding per operation -- the product kappa * g, the product (2 lam) * w, the sum
+ *   (G = 0: the first product alone); a QN_F32 gradient is widened, updated and rounded once.  Grid, element -> thread map and
+ *   the forward walk through the groups in LDS are qn_prior_fold_g's.  Workgroup 0 of a chain is the only writer of its sse
+ *   entry (the other columns of a strided sse are not touched): kappa * sse, plus P -- formed exactly as qn_prior_fold_g forms
+ *   it: the terms lam_g S_g added left to right, then c0 -- plus d0.  With kappa = 1, d0 = 0 and G >= 1 both outputs equal
+ *   qn_prior_fold_g's bit for bit.  No atomics, no fences: equal inputs give equal bits, a chain's result is the same launched
+ *   alone or among others, non-finite weights touch their own chain only.
+ *   QN_EINVAL with a message, before any pointer is touched: W, kappa or d0 NULL; G outside 0 .. 32; lam, c0 or seg NULL with
+ *   G >= 1; grad and sse both NULL; C outside 1 .. 65535; p < 1 or p < G; sse_stride < 1 with sse given; a gdtype other than the
+ *   two with grad given.
+ *
+ * qn_noise_gibbs: one Gibbs round, launched after the accept call, the adapt call and qn_hyper_gibbs (if any) of a step.
+ *   kappa [2, C] and d0 [2, C] are double-buffered by a parity of their OWN (slot noise_parity is read, slot 1 - noise_parity
+ *   written; the caller flips it once per round), cur_lp, best_lp [2, C] and step_ptr [2] by the step parity.  lam [C, G] and
+ *   c0 [C] are the slot of the weight prior that is current after those calls (read only; G = 0: not read).  Per chain, with
+ *   the step t just decided read from slot `parity` of step_ptr and S_g computed from cur [C, p] (the sums of qn_prior_fold_g):
+ *       F = (-cur_lp[parity, c] - lik_const) / h;   sse = ((F - d0) - P) / kappa          (the fold inverted, in this order)
+ *       1 / s2' ~ Gamma(a0 + n / 2, rate b0 + sse / 2);   kappa' = sigma0^2 / s2', d0' as above;   r = kappa' / kappa
+ *       sig[c, round + 1] = sqrt(s2')                 (sig [C, nrounds + 1] float64 or NULL; column 0 is the caller's)
+ *       sse_rec[c] = sse                              (sse_rec [C] float64 or NULL: the recovered SSE, written for every chain,
+ *                                                      kept or not -- for diagnostics and tests, nothing reads it)
+ *       grad_cur[c, j] <- grad_cur + (r - 1) * (grad_cur - (2 lam_g(j)) * cur[c, j])          (G = 0: grad_cur + (r - 1) * grad_cur)
+ *       cur_lp[1 - parity, c] = cur_lp[parity, c] - h * ((kappa' - kappa) * sse + (d0' - d0))
+ *       best_lp[1 - parity, c] = best_lp[parity, c];   step_ptr[1 - parity] = t;   lps[c, t] = the new cur_lp (0 <= t <= nmcmc):
+ *   the stored trace is that of the state step t + 1 starts from, as after qn_hyper_gibbs.  The caller flips both parities.
+ *   n_rows = N and n = N * o are host-known.  The Gamma variate is qn_hyper_gibbs's (Marsaglia & Tsang, the log test, at most
+ *   64 attempts, then shape / rate) with Philox keyed (seed, 2 t + 1, [chain0 + c : 24][12 : 4][index : 36]),
+ *   index = (attempt << 4) | block.  A chain whose recovered sse is not finite or is negative, or whose s2', kappa' or d0' is
+ *   not positive / finite, keeps kappa, d0, grad_cur, cur_lp and lps[c, t] (copied to the new slots; its sig column repeats
+ *   the previous one); no other chain is touched.  Every workgroup of a chain takes the whole decision itself from the slots
+ *   nobody writes in the launch: no atomics, no fences, no arrival counters; equal inputs give equal bits and nothing depends
+ *   on C or the chain's place.
+ *   QN_EINVAL with a message, before any pointer is touched: a0, b0 or sigma not > 0 or not finite; G outside 0 .. 32; C outside
+ *   1 .. 65535; p < 1 or p < G; chain0 < 0; nmcmc < 1; n_rows < 1 or n < n_rows; round outside 0 .. nrounds - 1; a parity other
+ *   than 0 / 1; a NULL pointer other than sig and sse_rec (and lam, c0, seg with G = 0). */
+int qn_noise_fold(const double* W, const double* kappa, const double* d0, const double* lam, const double* c0,
+                  const int64_t* seg, int G, void* grad, int gdtype, double* sse, int sse_stride, int C, int64_t p, void* stream);
+int qn_noise_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* kappa, double* d0,
+                   const double* lam, const double* c0, const int64_t* seg, double* sig, double* sse_rec, int64_t* step_ptr,
+                   double sigma, double a0, double b0, int n_rows, int64_t n, int G, int round, int nrounds, int C, int chain0, int64_t p,
+                   int nmcmc, uint64_t seed, int parity, int noise_parity, void* stream);
+
 /* Elliptical slice sampling on the device (Murray, Adams & MacKay 2010; build-only, the reference has no such sampler) for
  * the target L(w) N(w; 0, priorsigma^2 I), log L = gs sse + const, gs = -0.5 / sigma^2: no step size, no warm-up, only forward
  * calls.  The chains' steps are ASYNCHRONOUS: every chain has its own step t and shrink count j, and a launch of qn_ess_iter

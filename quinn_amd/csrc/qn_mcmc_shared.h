@@ -1,4 +1,4 @@
-// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_leap.hip, qn_hmc_adapt.hip, qn_temper.hip, qn_sgmcmc.hip, qn_prior.hip, qn_hyper.hip, qn_ess.hip, qn_nuts.hip): the Philox4x32-10 generator and
+// Device helpers shared by the sampler translation units (qn_mcmc.hip, qn_hmc_leap.hip, qn_hmc_adapt.hip, qn_temper.hip, qn_sgmcmc.hip, qn_prior.hip, qn_hyper.hip, qn_noise.hip, qn_ess.hip, qn_nuts.hip): the Philox4x32-10 generator and
 // its counter layout, the normal / uniform transforms, the 8-byte aligned pair accesses and the geometry + fixed-order block
 // sum of the HMC elementwise kernels.  Everything is internal linkage: each translation unit gets its own copy.
 #pragma once
@@ -34,7 +34,8 @@ struct Philox {
 // slice sampling (qn_ess.hip); 9 the momenta (index = column pair) and 10 the scalar uniforms (index = (kind << 32) | n: kind 0
 // the direction of doubling n, 1 the merge of doubling n, 2 the leaf whose n_leap was n) of the No-U-Turn sampler
 // (qn_nuts.hip); 11 the Gamma variates of the hyper-prior's Gibbs round (qn_hyper.hip; stream 2 t + 1, index =
-// (group << 16) | (attempt << 4) | block).  12-15 are free
+// (group << 16) | (attempt << 4) | block); 12 the Gamma variate of the noise level's Gibbs round (qn_noise.hip; stream
+// 2 t + 1, index = (attempt << 4) | block).  13-15 are free
 __device__ __forceinline__ uint64_t ctr_of(int chain, int purpose, uint64_t index) {
     return ((uint64_t)chain << 40) | ((uint64_t)purpose << 36) | (index & 0xFFFFFFFFFull);
 }

@@ -48,6 +48,17 @@ the precisions and refreshes the cached gradient and log density of the current 
 log density of (w, tau); the results gain 'tau' [C, nrounds + 1, G] (column 0: the initial precisions, tau0, else
 1 / priorsigma^2, else a0 / b0) and the engine the attribute `prior_groups` [(name, lo, hi)].  every = 0 never draws (fixed
 per-group scales from tau0).  Not with a ladder or a graph.  hyperprior = None (default) makes exactly the launches made before.
+
+`noiseprior` = dict(a0=, b0=, every=1, sigma_init=None) samples the noise level too (`quinn_amd.mcmc.noise` states the contract):
+one variance s2 per chain with 1 / s2 ~ Gamma(a0, rate b0), started at sigma_init, else at `sigma`.  The kernels keep the nominal
+`sigma`; the run state gains s['kappa'], s['d0'] [2, C] (double-buffered by the parity s['npar'] of their own), s['sig']
+[C, nrounds + 1] and the round counter s['nround'].  While s['kappa'] is set, ONE qn_noise_fold launch stands where qn_prior_fold /
+qn_prior_fold_g stood -- it carries the weight prior too: the current lam / c0 / seg of a hyper-prior, a one-group lam from
+`priorsigma`, or no group -- and every `every`-th step, warm-up included, is followed by one qn_noise_gibbs launch (order within
+a step: accept, adapt, hyper round, noise round).  'logpost' / 'maxpost' are then the JOINT log density of (w, s2[, tau]); the
+results gain 'sigma' [C, nrounds + 1] (column 0: the initial level).  every = 0 never draws: a fixed level sigma_init through the
+same fold (a0, b0 may be omitted).  Not with a ladder, a graph, a residual network or a float32 operator.  noiseprior = None
+(default) makes exactly the launches made before.
 """
 import numpy as np
 import torch
@@ -55,6 +66,7 @@ import torch
 from .. import _lib
 from .adapt import TARGET_ACCEPT, check_adapt_args, warmup_plan
 from .hyper import check_hyperprior, check_segments, fold_constants_g, group_segments, initial_tau
+from .noise import check_noiseprior, fold_constants_n
 from .tempering import check_temper_args, check_whole_ladders
 from .device_engine import DeviceEngine
 
@@ -67,7 +79,8 @@ class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
     def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
-                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None):
+                 target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None,
+                 noiseprior=None):
         # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
         # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
         # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
@@ -96,6 +109,18 @@ class DeviceHMC(DeviceEngine):
             self._seg = check_segments(seg, op.p)
             initial_tau(self._hyper, len(names), self.priorsigma)              # (a tau0 of the wrong length is refused here)
             self.prior_groups = [(n, int(lo), int(hi)) for n, lo, hi in zip(names, seg[:-1], seg[1:])]
+        # noise prior: the settings (None: the hand-set noise level `sigma`)
+        self._noise = check_noiseprior(noiseprior)
+        if self._noise is not None:
+            if self._ladder is not None:
+                raise ValueError("noiseprior does not run with a ladder (a tempered rung would need its own noise level)")
+            if self.use_graph:
+                raise ValueError("noiseprior does not run with use_graph=True (the round counter changes from launch to launch)")
+            if type(op.arch).__name__ != 'MLPArch':
+                raise ValueError(f"noiseprior: the noise level is sampled for plain MLPs, not for {type(op.arch).__name__}")
+            if op.tdt != torch.float64:
+                raise ValueError("noiseprior needs a float64 operator (the fold's rescaling of a float32 gradient would round it "
+                                 "a second time)")
 
     def _begin(self, s, st):
         """Enqueue the begin call of a step.  The entry point follows from what the state holds: s['beta'] (a ladder) -> _t,
@@ -132,7 +157,10 @@ class DeviceHMC(DeviceEngine):
         for j in range(self.L):
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
-            if s.get('lam') is not None:                                      # per-group precisions: the current slot of lam / c0
+            if s.get('kappa') is not None:                                    # a sampled noise level: ONE fold, the weight prior in it
+                self.op.noise_fold(s['q'], s['kappa'][s['npar']], s['d0'][s['npar']], *self._noise_prior(s), sse=s['sse'],
+                                   grad=s['gq'])
+            elif s.get('lam') is not None:                                    # per-group precisions: the current slot of lam / c0
                 self.op.prior_fold_g(s['q'], s['lam'][s['hpar']], s['c0'][s['hpar']], s['seg'], sse=s['sse'], grad=s['gq'])
             elif self._prior is not None:                                     # (the float64 positions, also under a float32 operator)
                 self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
@@ -172,6 +200,38 @@ class DeviceHMC(DeviceEngine):
         s['hpar'] ^= 1
         s['hround'] += 1
 
+    @staticmethod
+    def _noise_prior(s):
+        """(lam [C, G], c0 [C], seg [G + 1]) qn_noise_fold / qn_noise_gibbs read: the current slot of a hyper-prior, else the
+        one-group arrays of a scalar prior (s['plam']), else three None (G = 0)."""
+        if s.get('lam') is not None:
+            return s['lam'][s['hpar']], s['c0'][s['hpar']], s['seg']
+        if s.get('plam') is not None:
+            return s['plam'], s['pc0'], s['pseg']
+        return None, None, None
+
+    def _noise_step(self, s, nmcmc):
+        """Enqueue Gibbs round s['nround'] of the noise level after the step just decided, its adaptation and its hyper round:
+        like `_hyper_step` it reads slot s['par'] of the scalars and writes the other, and slot s['npar'] of kappa / d0 likewise."""
+        a0, b0, n = s['noise']
+        self.op.noise_gibbs(s['cur'], s['gcur'], s['cur_lp'], s['best_lp'], s['lps'], s['kappa'], s['d0'], *self._noise_prior(s),
+                            s['sig'], s['step'], self.sigma, a0, b0, n, s['nround'], self.chain0, self.seed, s['par'], s['npar'])
+        s['par'] ^= 1
+        s['npar'] ^= 1
+        s['nround'] += 1
+
+    def _gibbs_step(self, s, nmcmc, a=None):
+        """accept, adapt, hyper round, noise round: the launch order of a step under a hyper-prior and / or a noise prior (a
+        round after every s['hevery']-th / s['nevery']-th step; 0: never)."""
+        self._step(s, nmcmc)
+        if a is not None:
+            self._adapt_step(s, nmcmc, a)
+        s['nstep'] += 1
+        if s['hevery'] and s['nstep'] % s['hevery'] == 0:
+            self._hyper_step(s, nmcmc)
+        if s['nevery'] and s['nstep'] % s['nevery'] == 0:
+            self._noise_step(s, nmcmc)
+
     def _adapt_step(self, s, nmcmc, a):
         """Enqueue the adaptation after a warm-up step (a: that step's entry of `warmup_plan`); reads the step just decided
         from the slot of the step counter the accept call wrote, which is s['par'] after `_step`."""
@@ -190,7 +250,7 @@ class DeviceHMC(DeviceEngine):
         return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
                          target_accept=self.target_accept, adapt_mass=self.adapt_mass, ladder=self._ladder,
                          beta_min=self.beta_min, swap_every=self.swap_every, priorsigma=self.priorsigma,
-                         hyperprior=self._hyper)
+                         hyperprior=self._hyper, noiseprior=self._noise)
 
     def _check_groups(self, nmcmc, C, p):
         if self._ladder is not None:
@@ -208,6 +268,8 @@ class DeviceHMC(DeviceEngine):
                 out[k] = torch.cat([r[k] for r in res])
         if self._hyper is not None:
             out['tau'] = torch.cat([r['tau'] for r in res])
+        if self._noise is not None:
+            out['sigma'] = torch.cat([r['sigma'] for r in res])
 
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
@@ -232,12 +294,33 @@ class DeviceHMC(DeviceEngine):
                   'taus': torch.empty(C, (nmcmc // every if every else 0) + 1, G, dtype=f64, device=dev), 'hpar': 0, 'hround': 0,
                   'hyper': (hp['a0'], hp['b0']), 'nstep': 0}
             hs['taus'][:, 0] = torch.as_tensor(tau, dtype=f64, device=dev)
+        ns = None
+        if self._noise is not None:
+            # per chain: kappa = sigma^2 / s2 and the constant d0, double-buffered; the trace of the noise level; a scalar
+            # weight prior as one group on the device
+            npr, n = self._noise, self.op.N * self.op.Y.shape[1]
+            every = npr['every']
+            sig0 = self.sigma if npr['sigma_init'] is None else npr['sigma_init']
+            kappa, d0 = fold_constants_n(self.sigma, np.full(C, sig0 * sig0), n, self.op.N, npr['a0'], npr['b0'])
+            kappa, d0 = torch.as_tensor(kappa, dtype=f64, device=dev), torch.as_tensor(d0, dtype=f64, device=dev)
+            ns = {'kappa': torch.stack([kappa, kappa]), 'd0': torch.stack([d0, d0]), 'npar': 0, 'nround': 0,
+                  'sig': torch.empty(C, (nmcmc // every if every else 0) + 1, dtype=f64, device=dev),
+                  'noise': (npr['a0'], npr['b0'], n), 'nstep': 0}
+            ns['sig'][:, 0] = sig0
+            if hs is None and self._prior is not None:
+                ns.update(plam=torch.full((C, 1), self._prior[0], dtype=f64, device=dev),
+                          pc0=torch.full((C,), self._prior[1], dtype=f64, device=dev),
+                          pseg=torch.as_tensor([0, p], dtype=torch.int64, device=dev))
+            self.op.noise_fold(cur, kappa, d0, *self._noise_prior(dict(hs or {}, **ns)), sse=sse0, grad=g0)
+        elif hs is not None:
             self.op.prior_fold_g(cur, hs['lam'][0], hs['c0'][0], hs['seg'], sse=sse0, grad=g0)
         elif self._prior is not None:
             self.op.prior_fold(cur, *self._prior, sse=sse0, grad=g0)
         s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
         if hs is not None:
             s.update(hs)
+        if ns is not None:
+            s.update(ns)
         s.update({'gcur': g0.double() if f32op else g0.clone(),
                   'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),
                   'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
@@ -270,17 +353,10 @@ class DeviceHMC(DeviceEngine):
                 s['nstep'] = s.get('nstep', 0) + 1
                 if s['nstep'] % int(self.swap_every) == 0:
                     self._swap_step(s, nmcmc)
-        elif hs is not None and self._hyper['every']:
-            plain = self._step
-
-            def step(s, nmcmc, a=None):
-                """accept, adapt, Gibbs round: the launch order of a step under a hyper-prior."""
-                plain(s, nmcmc)
-                if a is not None:
-                    self._adapt_step(s, nmcmc, a)
-                s['nstep'] += 1
-                if s['nstep'] % self._hyper['every'] == 0:
-                    self._hyper_step(s, nmcmc)
+        elif (hs is not None and self._hyper['every']) or (ns is not None and self._noise['every']):
+            s['hevery'] = self._hyper['every'] if hs is not None else 0
+            s['nevery'] = self._noise['every'] if ns is not None else 0
+            step = self._gibbs_step
         if self.adapt:
             # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
             plan = warmup_plan(self.adapt, self.adapt_mass)
@@ -336,4 +412,6 @@ class DeviceHMC(DeviceEngine):
             out.update(beta=s['beta'], swap_rate=s['swap_acc'].double() / s['swap_try'].double(), replica=s['rep'])
         if hs is not None:
             out['tau'] = s['taus']
+        if ns is not None:
+            out['sigma'] = s['sig']
         return out

@@ -22,11 +22,11 @@ from .device_hmc import DeviceHMC
 class DeviceMALA(DeviceHMC):
     """Args as `MALA` (epsilon: step size, default 0.05) plus the engine's seed / chain0 / use_graph / groups and the warm-up
     arguments adapt / target_accept (default 0.574) / adapt_mass and the replica-exchange arguments ladder / beta_min /
-    swap_every and the hierarchical prior `hyperprior` of `DeviceHMC`."""
+    swap_every, the hierarchical prior `hyperprior` and the noise prior `noiseprior` of `DeviceHMC`."""
     _kind = 'mala'
 
     def __init__(self, op, sigma, epsilon=0.05, seed=0, chain0=0, use_graph=False, groups=None, adapt=0, target_accept=None,
-                 adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None):
+                 adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None, noiseprior=None):
         super().__init__(op, sigma, epsilon=epsilon, L=1, seed=seed, chain0=chain0, use_graph=use_graph, groups=groups,
                          adapt=adapt, target_accept=target_accept, adapt_mass=adapt_mass, ladder=ladder, beta_min=beta_min,
-                         swap_every=swap_every, priorsigma=priorsigma, hyperprior=hyperprior)
+                         swap_every=swap_every, priorsigma=priorsigma, hyperprior=hyperprior, noiseprior=noiseprior)

@@ -22,7 +22,7 @@ not where the posterior mass is): predict with `predict_ens` / `score`, not from
 
 `every` = 0 never draws: fixed per-group scales from `tau0`, the per-layer prior without a hyper-prior.
 
-Not covered: ARD scales per input, a hyper-prior on the noise level, any sampler but device HMC / MALA, ladders, graphs, RNet.
+Not covered: ARD scales per input, any sampler but device HMC / MALA, ladders, graphs, RNet.
 """
 import math
 
@@ -180,12 +180,13 @@ def u01(hi, lo):
     return (bits.astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
 
 
-def gamma_draw(seed, step, chain, group, shape, rate):
+def gamma_draw(seed, step, chain, group, shape, rate, purpose=PURPOSE_GAMMA):
     """Gamma(shape, rate) variates by Marsaglia & Tsang (2000), the log test only, exactly as qn_hyper_gibbs draws them:
     Philox keyed (seed, 2 step + 1, [chain : 24][11 : 4][index : 36]) with index = (group << 16) | (attempt << 4) | block;
     block 0 of an attempt gives the normal (Box-Muller in float64 on u01(words 0, 1), u01(words 2, 3)), block 1 the uniform of
     the test; shape < 1 draws at shape + 1 and multiplies by u^(1 / shape), u from index (group << 16) | (64 << 4).  At most 64
-    attempts, then shape / rate.  chain (GLOBAL id), group, shape and rate broadcast against each other."""
+    attempts, then shape / rate.  chain (GLOBAL id), group, shape and rate broadcast against each other.  `purpose`: the Philox
+    purpose in the place of 11 (12: the noise level's round, `quinn_amd.mcmc.noise`)."""
     chain, group, shape, rate = np.broadcast_arrays(np.asarray(chain, dtype=np.uint64), np.asarray(group, dtype=np.uint64),
                                                     np.asarray(shape, dtype=np.float64), np.asarray(rate, dtype=np.float64))
     dims = shape.shape
@@ -203,18 +204,18 @@ def gamma_draw(seed, step, chain, group, shape, rate):
             if todo.size == 0:
                 break
             idx = gbits[todo] | np.uint64(k << 4)
-            b0 = philox4x32(seed, stream, ctr_of(chain[todo], PURPOSE_GAMMA, idx))
+            b0 = philox4x32(seed, stream, ctr_of(chain[todo], purpose, idx))
             x = np.sqrt(-2.0 * np.log(u01(b0[:, 0], b0[:, 1]))) * np.cos(6.283185307179586 * u01(b0[:, 2], b0[:, 3]))
             t = 1.0 + c[todo] * x
             v = t * t * t
-            b1 = philox4x32(seed, stream, ctr_of(chain[todo], PURPOSE_GAMMA, idx | np.uint64(1)))
+            b1 = philox4x32(seed, stream, ctr_of(chain[todo], purpose, idx | np.uint64(1)))
             dd = d[todo]
             acc = (t > 0.0) & (np.log(u01(b1[:, 0], b1[:, 1])) < 0.5 * x * x + dd - dd * v + dd * np.log(np.where(t > 0.0, v, 1.0)))
             hit = todo[acc]
             gam = (dd * v)[acc]
             sm = small[hit]
             if sm.any():
-                bu = philox4x32(seed, stream, ctr_of(chain[hit], PURPOSE_GAMMA, gbits[hit] | np.uint64(GAMMA_TRIES << 4)))
+                bu = philox4x32(seed, stream, ctr_of(chain[hit], purpose, gbits[hit] | np.uint64(GAMMA_TRIES << 4)))
                 gam = np.where(sm, gam * np.exp(np.log(u01(bu[:, 0], bu[:, 1])) / shape[hit]), gam)
             out[hit] = gam / rate[hit]
             todo = todo[~acc]

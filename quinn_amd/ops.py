@@ -529,6 +529,81 @@ class BatchedMLP:
                                               int(chain0), p, lps.shape[1] - 1, int(seed), int(parity), int(hyper_parity),
                                               _lib.stream(self.device)), "qn_hyper_gibbs")
 
+    def _check_noise(self, what, kappa, d0, lam, c0, seg, C, lead=()):
+        """kappa, d0 [*lead, C] float64 contiguous device tensors; the weight prior lam [C, G], c0 [C], seg [G + 1] or three
+        None (G = 0); returns G."""
+        for t, name in ((kappa, "kappa"), (d0, "d0")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != lead + (C,) or \
+                    not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"{what}: {name} is a contiguous float64 device tensor {list(lead + (C,))}")
+        if lam is None and c0 is None and seg is None:
+            return 0
+        if lam is None or c0 is None or seg is None:
+            raise ValueError(f"{what}: lam, c0 and seg go together (all None: no weight prior)")
+        return self._check_groups(what, lam, c0, seg, C)
+
+    def noise_fold(self, W, kappa, d0, lam=None, c0=None, seg=None, sse=None, grad=None, sse_stride=1):
+        """Fold the per-chain noise level and the weight prior into the outputs of the gradient call just made at W [C, p]
+        float64 (qn_noise_fold, ONE launch on the current stream, in place; `quinn_amd.mcmc.noise.fold_n` restates it):
+        grad [C, p] <- kappa[c] grad + (2 lam[c, g(j)]) W, sse[c * sse_stride] <- (kappa[c] sse + sum_g lam[c, g] S_g + c0[c])
+        + d0[c].  kappa, d0 [C] float64 (`noise.fold_constants_n`); lam [C, G], c0 [C], seg [G + 1] as in `prior_fold_g`, or
+        all None: no weight prior."""
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
+            raise ValueError("noise_fold: W is a contiguous float64 device tensor [C, p]")
+        C, p = W.shape
+        G = self._check_noise("noise_fold", kappa, d0, lam, c0, seg, C)
+        gdt = _lib.QN_F64
+        if grad is not None:
+            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
+                raise ValueError("noise_fold: grad is a contiguous float64 / float32 tensor of W's shape")
+            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
+        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
+                                sse.numel() != C * int(sse_stride)):
+            raise ValueError("noise_fold: sse is a contiguous float64 tensor of C * sse_stride entries")
+        if C == 0:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_noise_fold(W.data_ptr(), kappa.data_ptr(), d0.data_ptr(), _ptr(lam), _ptr(c0), _ptr(seg), G,
+                                             _ptr(grad), gdt, _ptr(sse), int(sse_stride), C, p, _lib.stream(self.device)),
+                       "qn_noise_fold")
+
+    def noise_gibbs(self, cur, grad_cur, cur_lp, best_lp, lps, kappa, d0, lam, c0, seg, sig, step, sigma, a0, b0, n, round,
+                    chain0, seed, parity, noise_parity, sse_rec=None):
+        """One Gibbs round of the noise level after the step just decided (qn_noise_gibbs, one launch on the current stream;
+        `quinn_amd.mcmc.noise.gibbs_round` restates it): cur, grad_cur [C, p], cur_lp, best_lp, kappa, d0 [2, C], lps
+        [C, nmcmc + 1] float64; lam [C, G], c0 [C], seg [G + 1]: the CURRENT slot of the weight prior, or all None; step [2]
+        int64; sig [C, nrounds + 1] float64 or None; n = N * o entries of y.  Slot `parity` of the scalars and slot
+        `noise_parity` of kappa / d0 are read, the other slots written: the caller flips both.  sse_rec [C] float64 or None
+        receives the data SSE the round recovered (diagnostics; the engines pass None)."""
+        if not isinstance(cur, torch.Tensor) or cur.dtype != torch.float64 or cur.dim() != 2 or not cur.is_contiguous() or \
+                not cur.is_cuda:
+            raise ValueError("noise_gibbs: cur is a contiguous float64 device tensor [C, p]")
+        C, p = cur.shape
+        G = self._check_noise("noise_gibbs", kappa, d0, lam, c0, seg, C, lead=(2,))
+        for t, shape, name in ((grad_cur, (C, p), "grad_cur"), (cur_lp, (2, C), "cur_lp"), (best_lp, (2, C), "best_lp")):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"noise_gibbs: {name} is a contiguous float64 device tensor {list(shape)}")
+        if lps.dtype != torch.float64 or lps.dim() != 2 or lps.shape[0] != C or lps.shape[1] < 2 or not lps.is_contiguous():
+            raise ValueError("noise_gibbs: lps is a contiguous float64 tensor [C, nmcmc + 1], nmcmc >= 1")
+        if step.dtype != torch.int64 or step.numel() != 2 or not step.is_contiguous():
+            raise ValueError("noise_gibbs: step is the double-buffered int64 step counter [2]")
+        nrounds = int(round) + 1
+        if sig is not None:
+            if sig.dtype != torch.float64 or sig.dim() != 2 or sig.shape[0] != C or sig.shape[1] < 2 or not sig.is_contiguous():
+                raise ValueError("noise_gibbs: sig is a contiguous float64 tensor [C, nrounds + 1], nrounds >= 1")
+            nrounds = sig.shape[1] - 1
+        if sse_rec is not None and (sse_rec.dtype != torch.float64 or tuple(sse_rec.shape) != (C,) or not sse_rec.is_contiguous()
+                                    or not sse_rec.is_cuda):
+            raise ValueError("noise_gibbs: sse_rec is a contiguous float64 device tensor [C]")
+        if C == 0:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qn_noise_gibbs(cur.data_ptr(), grad_cur.data_ptr(), cur_lp.data_ptr(), best_lp.data_ptr(),
+                                              lps.data_ptr(), kappa.data_ptr(), d0.data_ptr(), _ptr(lam), _ptr(c0), _ptr(seg),
+                                              _ptr(sig), _ptr(sse_rec), step.data_ptr(), float(sigma), float(a0), float(b0), self.N, int(n), G,
+                                              int(round), nrounds, C, int(chain0), p, lps.shape[1] - 1, int(seed), int(parity),
+                                              int(noise_parity), _lib.stream(self.device)), "qn_noise_gibbs")
+
     def sse_pred(self, W, row_idx=None):
         s, pr, _ = self._call(W, row_idx, True, False)
         return s, pr

@@ -152,16 +152,23 @@ class QUiNNBase():
             raise ValueError(f"{type(self).__name__} keeps no data noise: pass noise=")
         return float(noise)
 
+    def _score_member_noise(self, noise, nsam, **ens_args):
+        """`(M,)` noise levels, one per member of the ensemble `_ens_weights(nsam, **ens_args)` draws, where the solver sampled
+        the noise level and `noise` is None; else None (one level for all members: `_score_noise`)."""
+        return None
+
     def score(self, x, y, noise=None, nsam=1000, crps=True, max_bytes=256 << 20, levels=scoring.DEFAULT_LEVELS, **ens_args):
         """Score the solver's `nsam`-member predictive ensemble against the targets y `(N, o)` at x: the dict of
         `scoring.summarise` (per entry lppd_k, p_waic_k, pit, crps_k, mean, var; scalars lppd, p_waic, elpd_waic, waic,
         se_elpd, nlpd, crps, rmse, coverage, pit_hist).  Member m predicts N(f_m(x), noise^2); `noise` defaults to the data
         noise of the last fit.  On the training data `waic` is the WAIC, on held-out data `nlpd` is the test negative log
         predictive density.  The weights are drawn ONCE (`_ens_weights`; ens_args as in `predict_ens`, e.g. NN_MCMC's
-        `nburn`, `chain='all'`), then x is walked in row chunks whose `M x rows x o` predictions fit `max_bytes`: one batched
+        `nburn`, `chain='all'`; a solver that sampled the noise level scores member m at its own level, through the
+        per-member variance V of `qn_pred_score`, unless `noise` is given), then x is walked in row chunks whose `M x rows x o` predictions fit `max_bytes`: one batched
         forward and one `qn_pred_score` per chunk, and only `6 x rows x o` doubles are downloaded.  An entry's scores do
         not depend on the chunking.  crps=False skips the pair pass, which costs O(M^2) per entry."""
-        sigma = self._score_noise(noise)
+        member = self._score_member_noise(noise, nsam, **ens_args)
+        sigma = self._score_noise(noise) if member is None else 0.0
         x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
         y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
         W = self._ens_weights(nsam, **ens_args)
@@ -176,7 +183,9 @@ class QUiNNBase():
             if F.dtype not in (torch.float32, torch.float64):
                 F = F.double()
             yt = torch.as_tensor(y[lo:hi].reshape(-1), device=F.device)
-            rows[:, lo * o:hi * o] = scoring.score_rows(F.reshape(M, -1), yt, sigma, None, what).cpu().numpy()
+            F = F.reshape(M, -1)
+            V = None if member is None else (torch.as_tensor(member, device=F.device) ** 2).to(F.dtype)[:, None].expand_as(F).contiguous()
+            rows[:, lo * o:hi * o] = scoring.score_rows(F, yt, sigma, V, what).cpu().numpy()
         return scoring.summarise(rows, y, levels)
 
     # -- figures (presentation only; same signatures and file names as quinn.py:106-260) ---------------
