@@ -1,5 +1,6 @@
 // Hierarchical Gaussian weight prior for the device HMC / MALA engines (build-only: the reference has no prior in NN_MCMC):
-//   qn_prior_fold_g : qn_prior_fold with one precision per weight GROUP and per chain, read from device arrays
+//   qn_prior_fold_g : qn_prior_fold with one precision per weight GROUP and per chain, read from device arrays (the one fold
+//                     kernel and its three entry points are in qn_prior.hip)
 //   qn_hyper_gibbs  : one exact Gibbs draw of every group's precision, and the refresh of the cached current state
 // Groups g < G <= 32 are the contiguous segments [seg[g], seg[g + 1]) of the flat weight vector, n_g entries each:
 //     w_j | tau_g ~ N(0, 1 / tau_g),   tau_g ~ Gamma(a0, rate b0),   tau_g | w ~ Gamma(a0 + n_g / 2, rate b0 + S_g / 2),
@@ -22,72 +23,14 @@ namespace {
 
 constexpr int PURPOSE_GAMMA = 11;         // Philox purpose of the Gamma variates (qn_mcmc_shared.h)
 
-// (GroupLds, load_segs, group_sumsq and gamma_draw: qn_group_shared.h, shared with qn_noise.hip)
+// (GroupLds, load_segs, group_sumsq, group_map, gamma_draw and the Gibbs rounds' common part: qn_group_shared.h)
 
-// g[base + e] <- g[base + e] + fac[group of e] * W[base + e] over this workgroup's chunk of the row: the element -> thread
-// map and the arithmetic of k_prior_fold (the product, then the sum, in float64, one rounding each; TG rounded once)
-template <typename TG>
-__device__ __forceinline__ void group_axpy(const GroupLds& l, const double* __restrict__ W, TG* __restrict__ g, int G, int64_t p) {
-    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
-    int gi = 0;
-    int64_t nxt = l.segs[1];                                               // the end of the thread's current group
-    double f = l.fac[0];
-    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
-        double gv[HUB], wv[HUB];
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            const bool in = e < hi;
-            gv[u] = in ? (double)g[e] : 0.0;
-            wv[u] = in ? W[e] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            if (e >= hi) break;
-            while (e >= nxt && gi + 1 < G) {                                // (elements only increase: a forward walk in LDS)
-                ++gi;
-                nxt = l.segs[gi + 1];
-                f = l.fac[gi];
-            }
-            const double t = f * wv[u];                                     // (two roundings: the product, then the sum)
-            g[e] = (TG)(gv[u] + t);
-        }
-    }
-}
-
-template <typename TG>
-__global__ __launch_bounds__(HBLK) void k_prior_fold_g(const double* __restrict__ W, const double* __restrict__ lam,
-                                                       const double* __restrict__ c0, const int64_t* __restrict__ seg, int G,
-                                                       TG* __restrict__ g, double* __restrict__ sse, int sse_stride, int64_t p) {
-    __shared__ GroupLds l;
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * p;
-    load_segs(l, seg, G, p);
-    if (threadIdx.x < G) l.fac[threadIdx.x] = 2.0 * lam[(int64_t)b * G + threadIdx.x];
-    __syncthreads();
-    if (g) group_axpy<TG>(l, W + base, g + base, G, p);
-    if (!sse || blockIdx.x != 0) return;                                   // (uniform over the workgroup)
-    group_sumsq(l, W + base, G);
-    if (threadIdx.x == 0) {
-        double term = lam[(int64_t)b * G] * l.S[0];
-        for (int k = 1; k < G; ++k) term = term + lam[(int64_t)b * G + k] * l.S[k];
-        double* out = sse + (int64_t)b * sse_stride;
-        term = term + c0[b];
-        *out = *out + term;
-    }
-}
-
-struct GibbsArgs {
-    int G, round, nrounds, C, chain0, nmcmc, par, hpar;
-    int64_t p;
-    uint64_t seed;
+struct GibbsArgs : GibbsCommon {          // (opar: the parity of lam / c0)
     double sigma, a0, b0, kconst;         // kconst = a0 log b0 - lgamma(a0), the constant of one log p(tau_g)
 };
 
 // Every workgroup of a chain takes the whole decision itself -- the sums of squares of the chain's row and the G draws, from
-// slot `hpar` of lam / c0 and slot `par` of the scalars, which nobody writes in this launch -- then refreshes its own chunk of
+// slot `opar` of lam / c0 and slot `par` of the scalars, which nobody writes in this launch -- then refreshes its own chunk of
 // the cached gradient; workgroup 0 writes the other slots.
 __global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double* __restrict__ cur, double* __restrict__ gcur,
                                                       double* cur_lp, double* best_lp, double* __restrict__ lps, double* lam,
@@ -98,7 +41,7 @@ __global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double*
     const int b = blockIdx.y, G = a.G;
     const int64_t base = (int64_t)b * a.p;
     const int64_t t = step_ptr[a.par];
-    const double* lo_ = lam + ((int64_t)a.hpar * a.C + b) * G;
+    const double* lo_ = lam + ((int64_t)a.opar * a.C + b) * G;
     load_segs(l, seg, G, a.p);
     if (threadIdx.x < G) lamo[threadIdx.x] = lo_[threadIdx.x];
     __syncthreads();
@@ -120,9 +63,10 @@ __global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double*
     __syncthreads();
     bool ok = true;                       // every new precision positive and finite, in lam's units too, and its term finite
     for (int g = 0; g < G; ++g) ok = ok && lamn[g] > 0.0 && lamn[g] < INFINITY && fabs(term[g]) < INFINITY;
-    if (ok) group_axpy<double>(l, cur + base, gcur + base, G, a.p);
+    // (two roundings: the product (2 (lam' - lam)) w, then the sum)
+    if (ok) group_map<double>(l, cur + base, gcur + base, G, a.p, 0.0, [](double gv, double t_) { return gv + t_; });
     if (blockIdx.x != 0) return;
-    double* ln_ = lam + ((int64_t)(1 - a.hpar) * a.C + b) * G;
+    double* ln_ = lam + ((int64_t)(1 - a.opar) * a.C + b) * G;
     if (threadIdx.x < G) {
         const int g = threadIdx.x;
         ln_[g] = ok ? lamn[g] : lamo[g];
@@ -132,8 +76,7 @@ __global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double*
         }
     }
     if (threadIdx.x == 0) {
-        const int so = a.par * a.C, sn = (1 - a.par) * a.C;
-        const double c0o = c0[a.hpar * a.C + b], clp = cur_lp[so + b];
+        const double c0o = c0[a.opar * a.C + b], clp = cur_lp[a.par * a.C + b];
         double nlp = clp, c0n = c0o;
         if (ok) {
             double dsum = (lamn[0] - lamo[0]) * l.S[0], tsum = term[0];
@@ -144,86 +87,26 @@ __global__ __launch_bounds__(HBLK) void k_hyper_gibbs(GibbsArgs a, const double*
             c0n = s2 * tsum;
             nlp = clp + (-0.5 / s2) * (dsum + (c0n - c0o));
         }
-        c0[(1 - a.hpar) * a.C + b] = c0n;
-        cur_lp[sn + b] = nlp;
-        best_lp[sn + b] = best_lp[so + b];
-        // the stored trace is that of the state step t + 1 starts from (the convention of qn_pt_swap)
-        if (ok && t >= 0 && t <= a.nmcmc) lps[(int64_t)b * (a.nmcmc + 1) + t] = nlp;
-        if (b == 0) step_ptr[1 - a.par] = t;                                   // no step was taken: the caller only flips its parity
+        c0[(1 - a.opar) * a.C + b] = c0n;
+        gibbs_other_slot(a, b, t, ok, nlp, cur_lp, best_lp, lps, step_ptr);
     }
 }
 
 }  // namespace
 
-extern "C" int qn_prior_fold_g(const double* W, const double* lam, const double* c0, const int64_t* seg, int G, void* grad,
-                               int gdtype, double* sse, int sse_stride, int C, int64_t p, void* stream) {
-    if (!W || !lam || !c0 || !seg) {
-        qn_set_error("qn_prior_fold_g: W, lam, c0 or seg is NULL");
-        return QN_EINVAL;
-    }
-    if (!grad && !sse) {
-        qn_set_error("qn_prior_fold_g: grad and sse are both NULL (nothing to fold the prior into)");
-        return QN_EINVAL;
-    }
-    if (G < 1 || G > GMAX) {
-        qn_set_error("qn_prior_fold_g: G = %d groups, 1 <= G <= %d", G, GMAX);
-        return QN_EINVAL;
-    }
-    if (C < 1 || C > 65535 || p < 1 || p < G) {
-        qn_set_error("qn_prior_fold_g: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d))", C, (long long)p, G);
-        return QN_EINVAL;
-    }
-    if (sse && sse_stride < 1) {
-        qn_set_error("qn_prior_fold_g: sse_stride = %d must be >= 1", sse_stride);
-        return QN_EINVAL;
-    }
-    if (grad && gdtype != QN_F64 && gdtype != QN_F32) {
-        qn_set_error("qn_prior_fold_g: gdtype = %d is neither QN_F64 nor QN_F32", gdtype);
-        return QN_EINVAL;
-    }
-    const dim3 grid(grad ? hmc_parts(p) : 1, C), blk(HBLK);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (grad && gdtype == QN_F32)
-        hipLaunchKernelGGL(k_prior_fold_g<float>, grid, blk, 0, st, W, lam, c0, seg, G, static_cast<float*>(grad), sse, sse_stride, p);
-    else
-        hipLaunchKernelGGL(k_prior_fold_g<double>, grid, blk, 0, st, W, lam, c0, seg, G, static_cast<double*>(grad), sse, sse_stride, p);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
-
 extern "C" int qn_hyper_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* lam,
                               double* c0, const int64_t* seg, double* taus, int64_t* step_ptr, double sigma, double a0,
                               double b0, int G, int round, int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed,
                               int parity, int hyper_parity, void* stream) {
-    if (!(a0 > 0.0) || !std::isfinite(a0) || !(b0 > 0.0) || !std::isfinite(b0) || !(sigma > 0.0) || !std::isfinite(sigma)) {
-        qn_set_error("qn_hyper_gibbs: a0 = %g, b0 = %g and sigma = %g must be > 0 and finite", a0, b0, sigma);
+    GibbsArgs a;
+    a.G = G; a.round = round; a.nrounds = nrounds; a.C = C; a.chain0 = chain0; a.nmcmc = nmcmc; a.par = parity; a.opar = hyper_parity;
+    a.p = p; a.seed = seed; a.sigma = sigma; a.a0 = a0; a.b0 = b0;
+    if (!gibbs_sizes_ok("qn_hyper_gibbs", 1, a, sigma, a0, b0) || !gibbs_round_ok("qn_hyper_gibbs", "hyper_parity", a))
         return QN_EINVAL;
-    }
-    if (G < 1 || G > GMAX) {
-        qn_set_error("qn_hyper_gibbs: G = %d groups, 1 <= G <= %d", G, GMAX);
-        return QN_EINVAL;
-    }
-    if (C < 1 || C > 65535 || p < 1 || p < G || chain0 < 0 || nmcmc < 1) {
-        qn_set_error("qn_hyper_gibbs: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d), chain0 = %d >= 0, nmcmc = %d >= 1)",
-                     C, (long long)p, G, chain0, nmcmc);
-        return QN_EINVAL;
-    }
-    if (nrounds < 1 || round < 0 || round >= nrounds) {
-        qn_set_error("qn_hyper_gibbs: round = %d outside 0 .. nrounds - 1 = %d", round, nrounds - 1);
-        return QN_EINVAL;
-    }
-    if ((parity != 0 && parity != 1) || (hyper_parity != 0 && hyper_parity != 1)) {
-        qn_set_error("qn_hyper_gibbs: parity = %d and hyper_parity = %d are 0 or 1", parity, hyper_parity);
-        return QN_EINVAL;
-    }
     if (!cur || !grad_cur || !cur_lp || !best_lp || !lps || !lam || !c0 || !seg || !step_ptr) {
         qn_set_error("qn_hyper_gibbs: a required pointer is NULL (only taus is optional)");
         return QN_EINVAL;
     }
-    GibbsArgs a;
-    a.G = G; a.round = round; a.nrounds = nrounds; a.C = C; a.chain0 = chain0; a.nmcmc = nmcmc; a.par = parity; a.hpar = hyper_parity;
-    a.p = p; a.seed = seed; a.sigma = sigma; a.a0 = a0; a.b0 = b0;
     a.kconst = a0 * std::log(b0) - std::lgamma(a0);
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_hyper_gibbs, dim3(hmc_parts(p), C), dim3(HBLK), 0, static_cast<hipStream_t>(stream), a, cur, grad_cur,

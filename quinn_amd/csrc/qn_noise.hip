@@ -1,7 +1,8 @@
 // Conjugate hyper-prior on the noise level of the Gaussian likelihood for the device HMC / MALA engines (build-only: the
 // reference's noise level is a hand-set scalar):
 //   qn_noise_fold  : the per-chain noise level AND the weight prior (none, scalar or per group) folded into a gradient call's
-//                    outputs in ONE launch; it stands where qn_prior_fold / qn_prior_fold_g stand
+//                    outputs in ONE launch; it stands where qn_prior_fold / qn_prior_fold_g stand (the one fold kernel and
+//                    its three entry points are in qn_prior.hip)
 //   qn_noise_gibbs : one exact Gibbs draw of every chain's noise precision, and the refresh of the cached current state
 // One variance s2_c per chain, shared by all n = N * o entries of y:
 //     y_k | w, s2 ~ N(M_w(x)_k, s2),   1 / s2 ~ Gamma(a0, rate b0),   1 / s2 | w, y ~ Gamma(a0 + n / 2, rate b0 + SSE(w) / 2).
@@ -21,86 +22,16 @@ namespace {
 
 constexpr int PURPOSE_NOISE = 12;         // Philox purpose of the noise precision's Gamma variate (qn_mcmc_shared.h)
 
-// g[e] <- op(g[e], fac[group of e] * W[e]) over this workgroup's chunk of the row: the grid, the element -> thread map and the
-// forward walk through the groups of qn_prior_fold_g (qn_hyper.hip).  G = 0: one group without a factor (op never sees t).
-template <typename TG, typename OP>
-__device__ __forceinline__ void group_map(const GroupLds& l, const double* __restrict__ W, TG* __restrict__ g, int G, int64_t p,
-                                          OP op) {
-    const int64_t chunk = (p + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * chunk, hi = lo + chunk < p ? lo + chunk : p;
-    int gi = 0;
-    int64_t nxt = G > 0 ? l.segs[1] : p;                                   // the end of the thread's current group
-    double f = G > 0 ? l.fac[0] : 0.0;
-    for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += (int64_t)HUB * HBLK) {
-        double gv[HUB], wv[HUB];
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            const bool in = e < hi;
-            gv[u] = in ? (double)g[e] : 0.0;
-            wv[u] = in ? W[e] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < HUB; ++u) {
-            const int64_t e = e0 + (int64_t)u * HBLK;
-            if (e >= hi) break;
-            while (e >= nxt && gi + 1 < G) {                                // (elements only increase: a forward walk in LDS)
-                ++gi;
-                nxt = l.segs[gi + 1];
-                f = l.fac[gi];
-            }
-            g[e] = (TG)op(gv[u], f * wv[u]);
-        }
-    }
-}
+// (GroupLds, load_segs, group_sumsq, group_map, prior_term, gamma_draw and the Gibbs rounds' common part: qn_group_shared.h)
 
-// the prior's part of the folded SSE, exactly as k_prior_fold_g forms it: the terms lam_g S_g left to right, then c0
-__device__ __forceinline__ double prior_term(const GroupLds& l, const double* __restrict__ lam, double c0, int G) {
-    double term = lam[0] * l.S[0];
-    for (int k = 1; k < G; ++k) term = term + lam[k] * l.S[k];
-    return term + c0;
-}
-
-template <typename TG>
-__global__ __launch_bounds__(HBLK) void k_noise_fold(const double* __restrict__ W, const double* __restrict__ kappa,
-                                                     const double* __restrict__ d0, const double* __restrict__ lam,
-                                                     const double* __restrict__ c0, const int64_t* __restrict__ seg, int G,
-                                                     TG* __restrict__ g, double* __restrict__ sse, int sse_stride, int64_t p) {
-    __shared__ GroupLds l;
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * p;
-    const double ka = kappa[b];
-    if (G > 0) {
-        load_segs(l, seg, G, p);
-        if (threadIdx.x < G) l.fac[threadIdx.x] = 2.0 * lam[(int64_t)b * G + threadIdx.x];
-        __syncthreads();
-    }
-    if (g) {
-        // three roundings: the product kappa g, the product (2 lam) w, the sum; G = 0: the first alone
-        if (G > 0) group_map<TG>(l, W + base, g + base, G, p, [ka](double gv, double t) { return ka * gv + t; });
-        else group_map<TG>(l, W + base, g + base, G, p, [ka](double gv, double) { return ka * gv; });
-    }
-    if (!sse || blockIdx.x != 0) return;                                   // (uniform over the workgroup)
-    if (G > 0) group_sumsq(l, W + base, G);
-    if (threadIdx.x == 0) {
-        double* out = sse + (int64_t)b * sse_stride;
-        double v = ka * *out;
-        if (G > 0) v = v + prior_term(l, lam + (int64_t)b * G, c0[b], G);
-        *out = v + d0[b];
-    }
-}
-
-struct NoiseArgs {
-    int G, round, nrounds, C, chain0, nmcmc, par, npar;
-    int64_t p;
-    uint64_t seed;
+struct NoiseArgs : GibbsCommon {          // (opar: the parity of kappa / d0)
     // s0sq = sigma0^2, h = 0.5 / sigma0^2, lik_const = (N / 2) log 2 pi + N log sigma0 (the accept kernel's), n = N * o,
     // nlog0 = N log(2 pi sigma0^2), kconst = a0 log b0 - lgamma(a0)
     double s0sq, h, lik_const, n, nlog0, a0, b0, kconst;
 };
 
 // Every workgroup of a chain takes the whole decision itself -- the prior's part of the cached density from the chain's row,
-// the recovered SSE, the draw, the new constants -- from slot `npar` of kappa / d0, slot `par` of the scalars and the current
+// the recovered SSE, the draw, the new constants -- from slot `opar` of kappa / d0, slot `par` of the scalars and the current
 // lam / c0, which nobody writes in this launch; then it refreshes its own chunk of the cached gradient; workgroup 0 writes the
 // other slots.
 __global__ __launch_bounds__(HBLK) void k_noise_gibbs(NoiseArgs a, const double* __restrict__ cur, double* __restrict__ gcur,
@@ -119,7 +50,7 @@ __global__ __launch_bounds__(HBLK) void k_noise_gibbs(NoiseArgs a, const double*
         __syncthreads();
         group_sumsq(l, cur + base, G);
     }
-    const double ko = kappa[a.npar * a.C + b], d0o = d0[a.npar * a.C + b], clp = cur_lp[a.par * a.C + b];
+    const double ko = kappa[a.opar * a.C + b], d0o = d0[a.opar * a.C + b], clp = cur_lp[a.par * a.C + b];
     if (threadIdx.x == 0) {
         // the data SSE of the current state: the fold inverted, in this order
         const double F = (-clp - a.lik_const) / a.h;
@@ -148,103 +79,39 @@ __global__ __launch_bounds__(HBLK) void k_noise_gibbs(NoiseArgs a, const double*
     if (ok) {
         // grad_cur + (r - 1) (grad_cur - (2 lam) w): the likelihood's part of the cached gradient rescaled, the prior's kept
         const double rm1 = dec[5];
-        if (G > 0) group_map<double>(l, cur + base, gcur + base, G, a.p, [rm1](double gv, double t_) { return gv + rm1 * (gv - t_); });
-        else group_map<double>(l, cur + base, gcur + base, G, a.p, [rm1](double gv, double) { return gv + rm1 * gv; });
+        if (G > 0) group_map<double>(l, cur + base, gcur + base, G, a.p, 0.0, [rm1](double gv, double t_) { return gv + rm1 * (gv - t_); });
+        else group_map<double>(l, cur + base, gcur + base, G, a.p, 0.0, [rm1](double gv, double) { return gv + rm1 * gv; });
     }
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int so = a.par * a.C, sn = (1 - a.par) * a.C, no = (1 - a.npar) * a.C;
+    const int no = (1 - a.opar) * a.C;
     double nlp = clp;
     if (ok) nlp = clp - a.h * ((dec[1] - ko) * dec[3] + (dec[2] - d0o));
     kappa[no + b] = ok ? dec[1] : ko;
     d0[no + b] = ok ? dec[2] : d0o;
-    cur_lp[sn + b] = nlp;
-    best_lp[sn + b] = best_lp[so + b];
-    // the stored trace is that of the state step t + 1 starts from (the convention of qn_pt_swap and qn_hyper_gibbs)
-    if (ok && t >= 0 && t <= a.nmcmc) lps[(int64_t)b * (a.nmcmc + 1) + t] = nlp;
     if (sse_rec) sse_rec[b] = dec[3];                                          // (whatever the decision: what the inversion gave)
     if (sig) {
         double* row = sig + (int64_t)b * (a.nrounds + 1) + a.round;
         row[1] = ok ? sqrt(dec[4]) : row[0];                                   // (a frozen chain repeats its last column)
     }
-    if (b == 0) step_ptr[1 - a.par] = t;                                       // no step was taken: the caller only flips its parity
+    gibbs_other_slot(a, b, t, ok, nlp, cur_lp, best_lp, lps, step_ptr);
 }
 
 }  // namespace
-
-extern "C" int qn_noise_fold(const double* W, const double* kappa, const double* d0, const double* lam, const double* c0,
-                             const int64_t* seg, int G, void* grad, int gdtype, double* sse, int sse_stride, int C, int64_t p,
-                             void* stream) {
-    if (!W || !kappa || !d0) {
-        qn_set_error("qn_noise_fold: W, kappa or d0 is NULL");
-        return QN_EINVAL;
-    }
-    if (G < 0 || G > GMAX) {
-        qn_set_error("qn_noise_fold: G = %d groups, 0 <= G <= %d", G, GMAX);
-        return QN_EINVAL;
-    }
-    if (G > 0 && (!lam || !c0 || !seg)) {
-        qn_set_error("qn_noise_fold: lam, c0 or seg is NULL with G = %d groups (G = 0: no weight prior)", G);
-        return QN_EINVAL;
-    }
-    if (!grad && !sse) {
-        qn_set_error("qn_noise_fold: grad and sse are both NULL (nothing to fold into)");
-        return QN_EINVAL;
-    }
-    if (C < 1 || C > 65535 || p < 1 || p < G) {
-        qn_set_error("qn_noise_fold: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d))", C, (long long)p, G);
-        return QN_EINVAL;
-    }
-    if (sse && sse_stride < 1) {
-        qn_set_error("qn_noise_fold: sse_stride = %d must be >= 1", sse_stride);
-        return QN_EINVAL;
-    }
-    if (grad && gdtype != QN_F64 && gdtype != QN_F32) {
-        qn_set_error("qn_noise_fold: gdtype = %d is neither QN_F64 nor QN_F32", gdtype);
-        return QN_EINVAL;
-    }
-    const dim3 grid(grad ? hmc_parts(p) : 1, C), blk(HBLK);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (grad && gdtype == QN_F32)
-        hipLaunchKernelGGL(k_noise_fold<float>, grid, blk, 0, st, W, kappa, d0, lam, c0, seg, G, static_cast<float*>(grad), sse,
-                           sse_stride, p);
-    else
-        hipLaunchKernelGGL(k_noise_fold<double>, grid, blk, 0, st, W, kappa, d0, lam, c0, seg, G, static_cast<double*>(grad), sse,
-                           sse_stride, p);
-    QN_HIP_CHECK(hipGetLastError());
-    return QN_OK;
-}
 
 extern "C" int qn_noise_gibbs(const double* cur, double* grad_cur, double* cur_lp, double* best_lp, double* lps, double* kappa,
                               double* d0, const double* lam, const double* c0, const int64_t* seg, double* sig,
                               double* sse_rec, int64_t* step_ptr, double sigma, double a0, double b0, int n_rows, int64_t n, int G, int round,
                               int nrounds, int C, int chain0, int64_t p, int nmcmc, uint64_t seed, int parity, int noise_parity,
                               void* stream) {
-    if (!(a0 > 0.0) || !std::isfinite(a0) || !(b0 > 0.0) || !std::isfinite(b0) || !(sigma > 0.0) || !std::isfinite(sigma)) {
-        qn_set_error("qn_noise_gibbs: a0 = %g, b0 = %g and sigma = %g must be > 0 and finite", a0, b0, sigma);
-        return QN_EINVAL;
-    }
-    if (G < 0 || G > GMAX) {
-        qn_set_error("qn_noise_gibbs: G = %d groups, 0 <= G <= %d", G, GMAX);
-        return QN_EINVAL;
-    }
-    if (C < 1 || C > 65535 || p < 1 || p < G || chain0 < 0 || nmcmc < 1) {
-        qn_set_error("qn_noise_gibbs: bad size (1 <= C = %d <= 65535, p = %lld >= max(1, G = %d), chain0 = %d >= 0, nmcmc = %d >= 1)",
-                     C, (long long)p, G, chain0, nmcmc);
-        return QN_EINVAL;
-    }
+    NoiseArgs a;
+    a.G = G; a.round = round; a.nrounds = nrounds; a.C = C; a.chain0 = chain0; a.nmcmc = nmcmc; a.par = parity; a.opar = noise_parity;
+    a.p = p; a.seed = seed; a.a0 = a0; a.b0 = b0; a.n = (double)n;
+    if (!gibbs_sizes_ok("qn_noise_gibbs", 0, a, sigma, a0, b0)) return QN_EINVAL;
     if (n_rows < 1 || n < n_rows) {
         qn_set_error("qn_noise_gibbs: n_rows = %d >= 1 rows and n = %lld >= n_rows entries of y", n_rows, (long long)n);
         return QN_EINVAL;
     }
-    if (nrounds < 1 || round < 0 || round >= nrounds) {
-        qn_set_error("qn_noise_gibbs: round = %d outside 0 .. nrounds - 1 = %d", round, nrounds - 1);
-        return QN_EINVAL;
-    }
-    if ((parity != 0 && parity != 1) || (noise_parity != 0 && noise_parity != 1)) {
-        qn_set_error("qn_noise_gibbs: parity = %d and noise_parity = %d are 0 or 1", parity, noise_parity);
-        return QN_EINVAL;
-    }
+    if (!gibbs_round_ok("qn_noise_gibbs", "noise_parity", a)) return QN_EINVAL;
     if (!cur || !grad_cur || !cur_lp || !best_lp || !lps || !kappa || !d0 || !step_ptr) {
         qn_set_error("qn_noise_gibbs: a required pointer is NULL (only sig and sse_rec are optional, and lam, c0, seg with G = 0)");
         return QN_EINVAL;
@@ -253,9 +120,6 @@ extern "C" int qn_noise_gibbs(const double* cur, double* grad_cur, double* cur_l
         qn_set_error("qn_noise_gibbs: lam, c0 or seg is NULL with G = %d groups (G = 0: no weight prior)", G);
         return QN_EINVAL;
     }
-    NoiseArgs a;
-    a.G = G; a.round = round; a.nrounds = nrounds; a.C = C; a.chain0 = chain0; a.nmcmc = nmcmc; a.par = parity; a.npar = noise_parity;
-    a.p = p; a.seed = seed; a.a0 = a0; a.b0 = b0; a.n = (double)n;
     a.s0sq = sigma * sigma;
     a.h = 0.5 / a.s0sq;
     a.lik_const = 0.5 * n_rows * std::log(2.0 * M_PI) + n_rows * std::log(sigma);

@@ -59,6 +59,12 @@ a step: accept, adapt, hyper round, noise round).  'logpost' / 'maxpost' are the
 results gain 'sigma' [C, nrounds + 1] (column 0: the initial level).  every = 0 never draws: a fixed level sigma_init through the
 same fold (a0, b0 may be omitted).  Not with a ladder, a graph, a residual network or a float32 operator.  noiseprior = None
 (default) makes exactly the launches made before.
+
+The three folds are one kernel (csrc/qn_prior.hip) behind three entry points, and the engine says the choice once: `_fold` picks
+qn_noise_fold, else qn_prior_fold_g, else qn_prior_fold, else nothing from what the run state holds, for the initial state and for
+every leapfrog gradient alike.  Likewise `_gibbs_step` is the one order after a step -- accept, adapt, exchange round, hyper
+round, noise round, a round after every s['severy']-th / s['hevery']-th / s['nevery']-th step (absent or 0: never) -- for the
+warm-up and for every run that has a round; a run without rounds takes plain `_step`s, and pairs of those are captured in a graph.
 """
 import numpy as np
 import torch
@@ -157,13 +163,7 @@ class DeviceHMC(DeviceEngine):
         for j in range(self.L):
             qc = s['q'] if s['qc'] is None else s['qc'].copy_(s['q'])          # float32 operator: cast the positions
             self.op.sse_grad(qc, out=(s['sse'], s['gq']))
-            if s.get('kappa') is not None:                                    # a sampled noise level: ONE fold, the weight prior in it
-                self.op.noise_fold(s['q'], s['kappa'][s['npar']], s['d0'][s['npar']], *self._noise_prior(s), sse=s['sse'],
-                                   grad=s['gq'])
-            elif s.get('lam') is not None:                                    # per-group precisions: the current slot of lam / c0
-                self.op.prior_fold_g(s['q'], s['lam'][s['hpar']], s['c0'][s['hpar']], s['seg'], sse=s['sse'], grad=s['gq'])
-            elif self._prior is not None:                                     # (the float64 positions, also under a float32 operator)
-                self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
+            self._fold(s, s['q'], s['sse'], s['gq'])                         # (the float64 positions, also under a float32 operator)
             self._leap(s, j == self.L - 1, st)
         g64 = s['gq'] if s['g64'] is None else s['g64'].copy_(s['gq'])
         args = (s['q'].data_ptr(), g64.data_ptr(), s['sse'].data_ptr(), s['kcur'].data_ptr(), s['kprop'].data_ptr(),
@@ -175,6 +175,17 @@ class DeviceHMC(DeviceEngine):
         else:
             _lib.check(self._L.qn_hmc_accept(*args, st), "qn_hmc_accept")
         s['par'] ^= 1
+
+    def _fold(self, s, W, sse, grad):
+        """Enqueue the ONE fold behind a gradient call at W, from what the state holds: s['kappa'] (a sampled noise level, the
+        weight prior in the same launch), else s['lam'] (per-group precisions: the current slot of lam / c0), else the scalar
+        prior, else nothing."""
+        if s.get('kappa') is not None:
+            self.op.noise_fold(W, s['kappa'][s['npar']], s['d0'][s['npar']], *self._noise_prior(s), sse=sse, grad=grad)
+        elif s.get('lam') is not None:
+            self.op.prior_fold_g(W, s['lam'][s['hpar']], s['c0'][s['hpar']], s['seg'], sse=sse, grad=grad)
+        elif self._prior is not None:
+            self.op.prior_fold(W, *self._prior, sse=sse, grad=grad)
 
     def _swap_step(self, s, nmcmc):
         """Enqueue exchange round s['round'] after the step just decided (and its adaptation); like `_adapt_step` it reads that
@@ -221,15 +232,18 @@ class DeviceHMC(DeviceEngine):
         s['nround'] += 1
 
     def _gibbs_step(self, s, nmcmc, a=None):
-        """accept, adapt, hyper round, noise round: the launch order of a step under a hyper-prior and / or a noise prior (a
-        round after every s['hevery']-th / s['nevery']-th step; 0: never)."""
+        """A step and what follows it, in the one order there is: accept, adapt (a: the step's entry of `warmup_plan`, None after
+        the warm-up), exchange round, hyper round, noise round -- a round after every s['severy']-th / s['hevery']-th /
+        s['nevery']-th step (absent or 0: never; the constructor refuses a ladder together with a Gibbs round)."""
         self._step(s, nmcmc)
         if a is not None:
             self._adapt_step(s, nmcmc, a)
-        s['nstep'] += 1
-        if s['hevery'] and s['nstep'] % s['hevery'] == 0:
+        n = s['nstep'] = s.get('nstep', 0) + 1
+        if s.get('severy') and n % s['severy'] == 0:
+            self._swap_step(s, nmcmc)
+        if s.get('hevery') and n % s['hevery'] == 0:
             self._hyper_step(s, nmcmc)
-        if s['nevery'] and s['nstep'] % s['nevery'] == 0:
+        if s.get('nevery') and n % s['nevery'] == 0:
             self._noise_step(s, nmcmc)
 
     def _adapt_step(self, s, nmcmc, a):
@@ -271,6 +285,59 @@ class DeviceHMC(DeviceEngine):
         if self._noise is not None:
             out['sigma'] = torch.cat([r['sigma'] for r in res])
 
+    def _hyper_state(self, C, nmcmc):
+        """The run state of a hyper-prior (empty without one): per chain and group lam = sigma^2 tau and the constant c0,
+        double-buffered; the group bounds; the trace of the precisions."""
+        if self._hyper is None:
+            return {}
+        dev, f64 = self.dev, torch.float64
+        hp, G = self._hyper, len(self._seg) - 1
+        every = hp['every']
+        tau = np.tile(initial_tau(hp, G, self.priorsigma), (C, 1))
+        lam, c0 = fold_constants_g(self.sigma, tau, self._seg, hp['a0'], hp['b0'])
+        lam, c0 = torch.as_tensor(lam, dtype=f64, device=dev), torch.as_tensor(c0, dtype=f64, device=dev)
+        hs = {'lam': torch.stack([lam, lam]), 'c0': torch.stack([c0, c0]), 'seg': torch.as_tensor(self._seg, device=dev),
+              'taus': torch.empty(C, (nmcmc // every if every else 0) + 1, G, dtype=f64, device=dev), 'hpar': 0, 'hround': 0,
+              'hyper': (hp['a0'], hp['b0']), 'hevery': every}
+        hs['taus'][:, 0] = torch.as_tensor(tau, dtype=f64, device=dev)
+        return hs
+
+    def _noise_state(self, C, p, nmcmc):
+        """The run state of a noise prior (empty without one): per chain kappa = sigma^2 / s2 and the constant d0,
+        double-buffered; the trace of the noise level; without a hyper-prior, a scalar weight prior as one group on the device."""
+        if self._noise is None:
+            return {}
+        dev, f64 = self.dev, torch.float64
+        npr, n = self._noise, self.op.N * self.op.Y.shape[1]
+        every = npr['every']
+        sig0 = self.sigma if npr['sigma_init'] is None else npr['sigma_init']
+        kappa, d0 = fold_constants_n(self.sigma, np.full(C, sig0 * sig0), n, self.op.N, npr['a0'], npr['b0'])
+        kappa, d0 = torch.as_tensor(kappa, dtype=f64, device=dev), torch.as_tensor(d0, dtype=f64, device=dev)
+        ns = {'kappa': torch.stack([kappa, kappa]), 'd0': torch.stack([d0, d0]), 'npar': 0, 'nround': 0,
+              'sig': torch.empty(C, (nmcmc // every if every else 0) + 1, dtype=f64, device=dev),
+              'noise': (npr['a0'], npr['b0'], n), 'nevery': every}
+        ns['sig'][:, 0] = sig0
+        if self._hyper is None and self._prior is not None:
+            ns.update(plam=torch.full((C, 1), self._prior[0], dtype=f64, device=dev),
+                      pc0=torch.full((C,), self._prior[1], dtype=f64, device=dev),
+                      pseg=torch.as_tensor([0, p], dtype=torch.int64, device=dev))
+        return ns
+
+    def _ladder_state(self, C, nmcmc):
+        """The run state of a ladder (empty without one): per-chain inverse temperature and step size epsilon / sqrt(beta_r);
+        the replica trace, which starts at the global chain ids; the exchange counters."""
+        if self._ladder is None:
+            return {}
+        dev, f64 = self.dev, torch.float64
+        R, nrounds = self._ladder.size, nmcmc // int(self.swap_every)
+        beta = torch.as_tensor(np.tile(self._ladder, C // R), dtype=f64, device=dev)
+        ids = torch.arange(self.chain0, self.chain0 + C, dtype=torch.int32, device=dev)
+        ls = {'beta': beta, 'rid': torch.stack([ids, ids]), 'rep': torch.zeros(C, nrounds + 1, dtype=torch.int32, device=dev),
+              'swap_acc': torch.zeros(C, dtype=torch.int64, device=dev), 'swap_try': torch.zeros(C, dtype=torch.int64, device=dev),
+              'round': 0, 'eps': self.epsilon / torch.sqrt(beta), 'severy': int(self.swap_every)}
+        ls['rep'][:, 0] = ids
+        return ls
+
     def _run_gen(self, nmcmc, param_ini, store_chain=True, verbose=False, chain_out=None):
         """The run as a generator: yields after every enqueued step (pair of steps under a graph); nothing is awaited."""
         check_adapt_args(self.adapt, self.target_accept, nmcmc)
@@ -282,45 +349,11 @@ class DeviceHMC(DeviceEngine):
         nk = int(self._L.qn_hmc_parts(p))
         f32op = self.op.tdt != f64
         sse0, g0 = self.op.sse_grad(cur if not f32op else cur.to(self.op.tdt))
-        hs = None
-        if self._hyper is not None:
-            # per chain and group: lam = sigma^2 tau and the constant c0, double-buffered; the trace of the precisions
-            hp, G = self._hyper, len(self._seg) - 1
-            every = hp['every']
-            tau = np.tile(initial_tau(hp, G, self.priorsigma), (C, 1))
-            lam, c0 = fold_constants_g(self.sigma, tau, self._seg, hp['a0'], hp['b0'])
-            lam, c0 = torch.as_tensor(lam, dtype=f64, device=dev), torch.as_tensor(c0, dtype=f64, device=dev)
-            hs = {'lam': torch.stack([lam, lam]), 'c0': torch.stack([c0, c0]), 'seg': torch.as_tensor(self._seg, device=dev),
-                  'taus': torch.empty(C, (nmcmc // every if every else 0) + 1, G, dtype=f64, device=dev), 'hpar': 0, 'hround': 0,
-                  'hyper': (hp['a0'], hp['b0']), 'nstep': 0}
-            hs['taus'][:, 0] = torch.as_tensor(tau, dtype=f64, device=dev)
-        ns = None
-        if self._noise is not None:
-            # per chain: kappa = sigma^2 / s2 and the constant d0, double-buffered; the trace of the noise level; a scalar
-            # weight prior as one group on the device
-            npr, n = self._noise, self.op.N * self.op.Y.shape[1]
-            every = npr['every']
-            sig0 = self.sigma if npr['sigma_init'] is None else npr['sigma_init']
-            kappa, d0 = fold_constants_n(self.sigma, np.full(C, sig0 * sig0), n, self.op.N, npr['a0'], npr['b0'])
-            kappa, d0 = torch.as_tensor(kappa, dtype=f64, device=dev), torch.as_tensor(d0, dtype=f64, device=dev)
-            ns = {'kappa': torch.stack([kappa, kappa]), 'd0': torch.stack([d0, d0]), 'npar': 0, 'nround': 0,
-                  'sig': torch.empty(C, (nmcmc // every if every else 0) + 1, dtype=f64, device=dev),
-                  'noise': (npr['a0'], npr['b0'], n), 'nstep': 0}
-            ns['sig'][:, 0] = sig0
-            if hs is None and self._prior is not None:
-                ns.update(plam=torch.full((C, 1), self._prior[0], dtype=f64, device=dev),
-                          pc0=torch.full((C,), self._prior[1], dtype=f64, device=dev),
-                          pseg=torch.as_tensor([0, p], dtype=torch.int64, device=dev))
-            self.op.noise_fold(cur, kappa, d0, *self._noise_prior(dict(hs or {}, **ns)), sse=sse0, grad=g0)
-        elif hs is not None:
-            self.op.prior_fold_g(cur, hs['lam'][0], hs['c0'][0], hs['seg'], sse=sse0, grad=g0)
-        elif self._prior is not None:
-            self.op.prior_fold(cur, *self._prior, sse=sse0, grad=g0)
+        extra = dict(self._hyper_state(C, nmcmc), **self._noise_state(C, p, nmcmc), nstep=0)
+        self._fold(extra, cur, sse0, g0)                                      # the initial state's, from slot 0 of every pair
         s = self._new_state(cur, sse0, nmcmc, store_chain, chain_out)
-        if hs is not None:
-            s.update(hs)
-        if ns is not None:
-            s.update(ns)
+        s.update(extra)
+        s.update(self._ladder_state(C, nmcmc))
         s.update({'gcur': g0.double() if f32op else g0.clone(),
                   'mom': torch.empty(C, p, dtype=f64, device=dev), 'q': torch.empty(C, p, dtype=f64, device=dev),
                   'gq': torch.empty(C, p, dtype=self.op.tdt, device=dev), 'sse': torch.empty(C, dtype=f64, device=dev),
@@ -328,53 +361,23 @@ class DeviceHMC(DeviceEngine):
                   'g64': torch.empty(C, p, dtype=f64, device=dev) if f32op else None,
                   'kcur': torch.empty(C, nk, dtype=f64, device=dev), 'kprop': torch.empty(C, nk, dtype=f64, device=dev)})
         i = 0
-        step = self._step
-        eps0 = self.epsilon
-        if self._ladder is not None:
-            # per-chain inverse temperature and step size epsilon / sqrt(beta_r); the replica trace starts at the global chain ids
-            R, nrounds = self._ladder.size, nmcmc // int(self.swap_every)
-            s['beta'] = torch.as_tensor(np.tile(self._ladder, C // R), dtype=f64, device=dev)
-            ids = torch.arange(self.chain0, self.chain0 + C, dtype=torch.int32, device=dev)
-            s['rid'] = torch.stack([ids, ids])
-            s['rep'] = torch.zeros(C, nrounds + 1, dtype=torch.int32, device=dev)
-            s['rep'][:, 0] = ids
-            s['swap_acc'] = torch.zeros(C, dtype=torch.int64, device=dev)
-            s['swap_try'] = torch.zeros(C, dtype=torch.int64, device=dev)
-            s['round'] = 0
-            eps0 = self.epsilon / torch.sqrt(s['beta'])
-            s['eps'] = eps0.clone()
-            plain = self._step
-
-            def step(s, nmcmc, a=None):
-                """accept, adapt, swap: the launch order of a tempered step."""
-                plain(s, nmcmc)
-                if a is not None:
-                    self._adapt_step(s, nmcmc, a)
-                s['nstep'] = s.get('nstep', 0) + 1
-                if s['nstep'] % int(self.swap_every) == 0:
-                    self._swap_step(s, nmcmc)
-        elif (hs is not None and self._hyper['every']) or (ns is not None and self._noise['every']):
-            s['hevery'] = self._hyper['every'] if hs is not None else 0
-            s['nevery'] = self._noise['every'] if ns is not None else 0
-            step = self._gibbs_step
+        # a run without rounds (and every run under a graph: the constructor refuses rounds there) takes plain steps
+        step = self._gibbs_step if s.get('severy') or s.get('hevery') or s.get('nevery') else self._step
         if self.adapt:
             # warm-up: direct launches, every step followed by its adaptation; afterwards eps / scale are frozen device arrays
             plan = warmup_plan(self.adapt, self.adapt_mass)
             mass = any(a['finish'] for a in plan)
+            s['da'] = torch.zeros(C, 4, dtype=f64, device=dev)          # (mu, Hbar, logbar, logeps)
             if self._ladder is None:
                 s['eps'] = torch.full((C,), self.epsilon, dtype=f64, device=dev)
-            s['da'] = torch.zeros(C, 4, dtype=f64, device=dev)          # (mu, Hbar, logbar, logeps)
-            s['da'][:, 0] = np.log(10 * self.epsilon) if self._ladder is None else torch.log(10 * eps0)
-            s['da'][:, 3] = np.log(self.epsilon) if self._ladder is None else torch.log(eps0)
+                s['da'][:, 0], s['da'][:, 3] = np.log(10 * self.epsilon), np.log(self.epsilon)
+            else:
+                s['da'][:, 0], s['da'][:, 3] = torch.log(10 * s['eps']), torch.log(s['eps'])
             s['scale'] = torch.ones(C, p, dtype=f64, device=dev) if mass else None
             s['wmean'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             s['wm2'] = torch.zeros(C, p, dtype=f64, device=dev) if mass else None
             for a in plan:
-                if step == self._step:
-                    step(s, nmcmc)
-                    self._adapt_step(s, nmcmc, a)
-                else:
-                    step(s, nmcmc, a)
+                self._gibbs_step(s, nmcmc, a)
                 i += 1
                 yield
         if self.use_graph and nmcmc - i >= 4:
@@ -410,8 +413,8 @@ class DeviceHMC(DeviceEngine):
             out.update(epsilon=s['eps'], mass_scale=s['scale'], nwarm=self.adapt)
         if self._ladder is not None:
             out.update(beta=s['beta'], swap_rate=s['swap_acc'].double() / s['swap_try'].double(), replica=s['rep'])
-        if hs is not None:
+        if self._hyper is not None:
             out['tau'] = s['taus']
-        if ns is not None:
+        if self._noise is not None:
             out['sigma'] = s['sig']
         return out

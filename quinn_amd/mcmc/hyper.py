@@ -1,6 +1,6 @@
 """Hierarchical Gaussian weight prior for the device HMC / MALA engines (build-only: the reference has no prior in `NN_MCMC`):
 per-group precisions with a conjugate Gamma hyper-prior, Gibbs-sampled on the device (Neal 1996).  The contract of
-qn_prior_fold_g and qn_hyper_gibbs (csrc/qn_hyper.hip, include/quinn_amd.h) restated in numpy, and the authority for the draw.
+qn_prior_fold_g and qn_hyper_gibbs (csrc/qn_prior.hip, csrc/qn_hyper.hip, include/quinn_amd.h) restated in numpy, and the authority for the draw.
 
 Groups g = 0 .. G - 1 (G <= 32) are contiguous segments [seg[g], seg[g + 1]) of the flat weight vector, n_g entries each:
 

@@ -1,5 +1,5 @@
 """Conjugate hyper-prior on the noise level `datanoise` for the device HMC / MALA engines (build-only: the reference's noise
-level is a hand-set scalar), Gibbs-sampled on the device.  The contract of qn_noise_fold and qn_noise_gibbs (csrc/qn_noise.hip,
+level is a hand-set scalar), Gibbs-sampled on the device.  The contract of qn_noise_fold and qn_noise_gibbs (csrc/qn_prior.hip, csrc/qn_noise.hip,
 include/quinn_amd.h) restated in numpy, and the authority for the draw.
 
 One noise variance s2_c per chain, shared by all n = N * o entries of y (N rows, o outputs):

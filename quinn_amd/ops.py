@@ -438,22 +438,34 @@ class BatchedMLP:
         s, _, g = self._call(W, row_idx, False, True, out=out)
         return s, g
 
+    @staticmethod
+    def _check_rows(what, W, name="W"):
+        """W (or cur) of a fold / Gibbs round: a contiguous float64 device tensor [C, p]; returns (C, p)."""
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
+            raise ValueError(f"{what}: {name} is a contiguous float64 device tensor [C, p]")
+        return W.shape
+
+    @staticmethod
+    def _check_fold(what, W, grad, sse, sse_stride):
+        """The outputs of a fold at W [C, p] (checked by `_check_rows`): grad [C, p] float64 / float32 and sse (C * sse_stride
+        float64), either None; returns the QN_* code of grad's dtype."""
+        gdt = _lib.QN_F64
+        if grad is not None:
+            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
+                raise ValueError(f"{what}: grad is a contiguous float64 / float32 tensor of W's shape")
+            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
+        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
+                                sse.numel() != W.shape[0] * int(sse_stride)):
+            raise ValueError(f"{what}: sse is a contiguous float64 tensor of C * sse_stride entries")
+        return gdt
+
     def prior_fold(self, W, lam, c0, sse=None, grad=None, sse_stride=1):
         """Fold the Gaussian weight prior into the outputs of the forward / gradient call just made at W [C, p] float64
         (qn_prior_fold, one launch on the current stream, in place): grad [C, p] float64 / float32 += (2 lam) W,
         sse[c * sse_stride] += lam |W[c]|^2 + c0 (sse float64, [C] or [C, sse_stride]: column 0 receives the term).
         `quinn_amd.mcmc.prior.fold_constants` gives (lam, c0)."""
-        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
-            raise ValueError("prior_fold: W is a contiguous float64 device tensor [C, p]")
-        C, p = W.shape
-        gdt = _lib.QN_F64
-        if grad is not None:
-            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
-                raise ValueError("prior_fold: grad is a contiguous float64 / float32 tensor of W's shape")
-            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
-        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
-                                sse.numel() != C * int(sse_stride)):
-            raise ValueError("prior_fold: sse is a contiguous float64 tensor of C * sse_stride entries")
+        C, p = self._check_rows("prior_fold", W)
+        gdt = self._check_fold("prior_fold", W, grad, sse, sse_stride)
         if C == 0:
             return
         with torch.cuda.device(self.device):
@@ -477,23 +489,27 @@ class BatchedMLP:
         the current stream, in place): grad [C, p] += (2 lam[c, g(j)]) W, sse[c * sse_stride] += sum_g lam[c, g] S_g + c0[c].
         lam [C, G], c0 [C] float64; seg [G + 1] int64, the group bounds (`quinn_amd.mcmc.hyper.fold_constants_g`,
         `group_segments`)."""
-        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
-            raise ValueError("prior_fold_g: W is a contiguous float64 device tensor [C, p]")
-        C, p = W.shape
+        C, p = self._check_rows("prior_fold_g", W)
         G = self._check_groups("prior_fold_g", lam, c0, seg, C)
-        gdt = _lib.QN_F64
-        if grad is not None:
-            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
-                raise ValueError("prior_fold_g: grad is a contiguous float64 / float32 tensor of W's shape")
-            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
-        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
-                                sse.numel() != C * int(sse_stride)):
-            raise ValueError("prior_fold_g: sse is a contiguous float64 tensor of C * sse_stride entries")
+        gdt = self._check_fold("prior_fold_g", W, grad, sse, sse_stride)
         if C == 0:
             return
         with torch.cuda.device(self.device):
             _lib.check(self._L.qn_prior_fold_g(W.data_ptr(), lam.data_ptr(), c0.data_ptr(), seg.data_ptr(), G, _ptr(grad), gdt,
                                                _ptr(sse), int(sse_stride), C, p, _lib.stream(self.device)), "qn_prior_fold_g")
+
+    @staticmethod
+    def _check_gibbs(what, cur, grad_cur, cur_lp, best_lp, lps, step):
+        """The state a Gibbs round refreshes, cur [C, p] checked by `_check_rows`: grad_cur [C, p], cur_lp, best_lp [2, C], lps
+        [C, nmcmc + 1] float64 and step [2] int64."""
+        C, p = cur.shape
+        for t, shape, name in ((grad_cur, (C, p), "grad_cur"), (cur_lp, (2, C), "cur_lp"), (best_lp, (2, C), "best_lp")):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"{what}: {name} is a contiguous float64 device tensor {list(shape)}")
+        if lps.dtype != torch.float64 or lps.dim() != 2 or lps.shape[0] != C or lps.shape[1] < 2 or not lps.is_contiguous():
+            raise ValueError(f"{what}: lps is a contiguous float64 tensor [C, nmcmc + 1], nmcmc >= 1")
+        if step.dtype != torch.int64 or step.numel() != 2 or not step.is_contiguous():
+            raise ValueError(f"{what}: step is the double-buffered int64 step counter [2]")
 
     def hyper_gibbs(self, cur, grad_cur, cur_lp, best_lp, lps, lam, c0, seg, taus, step, sigma, a0, b0, round, chain0, seed,
                     parity, hyper_parity):
@@ -502,18 +518,9 @@ class BatchedMLP:
         [C, nmcmc + 1], lam [2, C, G], c0 [2, C] float64; seg [G + 1], step [2] int64; taus [C, nrounds + 1, G] float64 or
         None.  Slot `parity` of the scalars and slot `hyper_parity` of lam / c0 are read, the other slots written: the caller
         flips both."""
-        if not isinstance(cur, torch.Tensor) or cur.dtype != torch.float64 or cur.dim() != 2 or not cur.is_contiguous() or \
-                not cur.is_cuda:
-            raise ValueError("hyper_gibbs: cur is a contiguous float64 device tensor [C, p]")
-        C, p = cur.shape
+        C, p = self._check_rows("hyper_gibbs", cur, "cur")
         G = self._check_groups("hyper_gibbs", lam, c0, seg, C, lead=(2,))
-        for t, shape, name in ((grad_cur, (C, p), "grad_cur"), (cur_lp, (2, C), "cur_lp"), (best_lp, (2, C), "best_lp")):
-            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError(f"hyper_gibbs: {name} is a contiguous float64 device tensor {list(shape)}")
-        if lps.dtype != torch.float64 or lps.dim() != 2 or lps.shape[0] != C or lps.shape[1] < 2 or not lps.is_contiguous():
-            raise ValueError("hyper_gibbs: lps is a contiguous float64 tensor [C, nmcmc + 1], nmcmc >= 1")
-        if step.dtype != torch.int64 or step.numel() != 2 or not step.is_contiguous():
-            raise ValueError("hyper_gibbs: step is the double-buffered int64 step counter [2]")
+        self._check_gibbs("hyper_gibbs", cur, grad_cur, cur_lp, best_lp, lps, step)
         nrounds = int(round) + 1
         if taus is not None:
             if taus.dtype != torch.float64 or taus.dim() != 3 or taus.shape[0] != C or taus.shape[2] != G or \
@@ -548,18 +555,9 @@ class BatchedMLP:
         grad [C, p] <- kappa[c] grad + (2 lam[c, g(j)]) W, sse[c * sse_stride] <- (kappa[c] sse + sum_g lam[c, g] S_g + c0[c])
         + d0[c].  kappa, d0 [C] float64 (`noise.fold_constants_n`); lam [C, G], c0 [C], seg [G + 1] as in `prior_fold_g`, or
         all None: no weight prior."""
-        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or not W.is_contiguous() or not W.is_cuda:
-            raise ValueError("noise_fold: W is a contiguous float64 device tensor [C, p]")
-        C, p = W.shape
+        C, p = self._check_rows("noise_fold", W)
         G = self._check_noise("noise_fold", kappa, d0, lam, c0, seg, C)
-        gdt = _lib.QN_F64
-        if grad is not None:
-            if grad.shape != W.shape or grad.dtype not in (torch.float64, torch.float32) or not grad.is_contiguous():
-                raise ValueError("noise_fold: grad is a contiguous float64 / float32 tensor of W's shape")
-            gdt = _lib.QN_F64 if grad.dtype == torch.float64 else _lib.QN_F32
-        if sse is not None and (sse.dtype != torch.float64 or not sse.is_contiguous() or sse_stride < 1 or
-                                sse.numel() != C * int(sse_stride)):
-            raise ValueError("noise_fold: sse is a contiguous float64 tensor of C * sse_stride entries")
+        gdt = self._check_fold("noise_fold", W, grad, sse, sse_stride)
         if C == 0:
             return
         with torch.cuda.device(self.device):
@@ -575,18 +573,9 @@ class BatchedMLP:
         int64; sig [C, nrounds + 1] float64 or None; n = N * o entries of y.  Slot `parity` of the scalars and slot
         `noise_parity` of kappa / d0 are read, the other slots written: the caller flips both.  sse_rec [C] float64 or None
         receives the data SSE the round recovered (diagnostics; the engines pass None)."""
-        if not isinstance(cur, torch.Tensor) or cur.dtype != torch.float64 or cur.dim() != 2 or not cur.is_contiguous() or \
-                not cur.is_cuda:
-            raise ValueError("noise_gibbs: cur is a contiguous float64 device tensor [C, p]")
-        C, p = cur.shape
+        C, p = self._check_rows("noise_gibbs", cur, "cur")
         G = self._check_noise("noise_gibbs", kappa, d0, lam, c0, seg, C, lead=(2,))
-        for t, shape, name in ((grad_cur, (C, p), "grad_cur"), (cur_lp, (2, C), "cur_lp"), (best_lp, (2, C), "best_lp")):
-            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError(f"noise_gibbs: {name} is a contiguous float64 device tensor {list(shape)}")
-        if lps.dtype != torch.float64 or lps.dim() != 2 or lps.shape[0] != C or lps.shape[1] < 2 or not lps.is_contiguous():
-            raise ValueError("noise_gibbs: lps is a contiguous float64 tensor [C, nmcmc + 1], nmcmc >= 1")
-        if step.dtype != torch.int64 or step.numel() != 2 or not step.is_contiguous():
-            raise ValueError("noise_gibbs: step is the double-buffered int64 step counter [2]")
+        self._check_gibbs("noise_gibbs", cur, grad_cur, cur_lp, best_lp, lps, step)
         nrounds = int(round) + 1
         if sig is not None:
             if sig.dtype != torch.float64 or sig.dim() != 2 or sig.shape[0] != C or sig.shape[1] < 2 or not sig.is_contiguous():

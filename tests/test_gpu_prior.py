@@ -1,6 +1,6 @@
 """GPU: the Gaussian weight prior of `NN_MCMC` (qn_prior_fold behind every forward / gradient call of the device engines).  The
 kernel is checked against `prior.fold` (gradient bit for bit, sum of squares to the bound of any summation order, run-to-run
-and launch-split reproducibility, non-finite rows), every engine's stored trace against the host formula with the prior, one HMC
+and launch-split reproducibility, non-finite rows; the three fold entry points, one kernel, agree in every bit), every engine's stored trace against the host formula with the prior, one HMC
 step against the numpy leapfrog, the host gradient against central differences, the samplers in distribution on a posterior
 that exists only because of the prior, and the default (no prior), graph and group paths for bit-identity."""
 import math
@@ -115,6 +115,71 @@ def test_non_finite_weights_stay_in_their_chain(p):
         mask = np.ones(p, dtype=bool)
         mask[p // 2] = False
         assert np.array_equal(got_g[1, mask], clean_g[1, mask])
+
+
+# ------------------------------------------------------------------- one fold kernel behind three entry points
+def _three_folds(W, grad=None, sse=None, stride=1):
+    """The scalar prior (LAM, C0) through qn_prior_fold, through qn_prior_fold_g as one group [0, p) with lam[c, 0] = LAM,
+    c0[c] = C0, and through qn_noise_fold with that group, kappa = 1 and d0 = 0 -> three (grad', sse') pairs, numpy."""
+    L = _lib.lib()
+    C, p = W.shape
+    dev = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    Wt, lam, c0, seg = dev(W), dev(np.full((C, 1), LAM)), dev(np.full(C, C0)), dev(np.array([0, p], dtype=np.int64))
+    kappa, d0 = dev(np.ones(C)), dev(np.zeros(C))
+    gdt = _lib.QN_F32 if grad is not None and grad.dtype == np.float32 else _lib.QN_F64
+    out = []
+    for name in ("qn_prior_fold", "qn_prior_fold_g", "qn_noise_fold"):
+        gt, st = dev(grad), dev(sse)
+        rest = (ptr(gt), gdt, ptr(st), stride, C, p, None)
+        group = (lam.data_ptr(), c0.data_ptr(), seg.data_ptr(), 1)
+        args = {"qn_prior_fold": (LAM, C0), "qn_prior_fold_g": group, "qn_noise_fold": (kappa.data_ptr(), d0.data_ptr()) + group}
+        _lib.check(getattr(L, name)(Wt.data_ptr(), *args[name], *rest), name)
+        torch.cuda.synchronize()
+        out.append((None if gt is None else gt.cpu().numpy(), None if st is None else st.cpu().numpy()))
+    return out
+
+
+def _same_bits(a, b):
+    return (a is None and b is None) or (a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)))
+
+
+@pytest.mark.parametrize("p", [1, 7, 1024, 1025, 4099])
+def test_the_three_entry_points_are_one_fold_bit_for_bit(p):
+    """C = 3; p = 1024 / 1025 straddle the chunk at which a chain goes from one workgroup to two, 4099 gives five with a ragged
+    tail.  Gradient (float64, float32) AND SSE of the three entry points agree in every bit, for sse_stride 1 and 3, and the SSE
+    is the same with and without a gradient (another grid).  The SSE is positive: kappa = 1, d0 = 0 alters no bit of it."""
+    rs = np.random.RandomState(300 + p)
+    C = 3
+    W, g64 = rs.randn(C, p), 3.0 * rs.randn(C, p)
+    for stride in (1, 3):
+        sse = 10.0 + 40.0 * rs.rand(C * stride)
+        assert C0 + sse.min() > 0.0
+        alone = _three_folds(W, sse=sse, stride=stride)                       # grad NULL: one workgroup per chain
+        for g in (g64, g64.astype(np.float32)):
+            both = _three_folds(W, grad=g, sse=sse, stride=stride)
+            only_g = _three_folds(W, grad=g, stride=stride)                   # sse NULL
+            for k in (1, 2):
+                assert _same_bits(both[k][0], both[0][0]) and _same_bits(both[k][1], both[0][1]), (stride, g.dtype, k)
+                assert _same_bits(only_g[k][0], both[0][0]) and only_g[k][1] is None
+                assert _same_bits(alone[k][1], both[0][1]) and alone[k][0] is None
+            assert _same_bits(only_g[0][0], both[0][0]) and _same_bits(alone[0][1], both[0][1])
+            assert both[0][0].dtype == g.dtype and np.all(both[0][1].reshape(C, stride)[:, 0] > 0.0)
+            assert np.array_equal(both[0][1].reshape(C, stride)[:, 1:], sse.reshape(C, stride)[:, 1:])
+
+
+@pytest.mark.parametrize("p", [1, 7, 1024, 1025, 4099])
+def test_a_nan_row_leaves_the_other_rows_of_every_entry_point_as_a_launch_without_it(p):
+    rs = np.random.RandomState(400 + p)
+    W, g, sse = rs.randn(3, p), rs.randn(3, p), 5.0 + rs.rand(3)
+    W[1, p // 2] = np.nan
+    keep = [0, 2]
+    for gg in (g, g.astype(np.float32)):
+        with_row = _three_folds(W, grad=gg, sse=sse)
+        without = _three_folds(W[keep], grad=gg[keep], sse=sse[keep])
+        for (got_g, got_s), (want_g, want_s) in zip(with_row, without):
+            assert np.isnan(got_s[1]) and np.isnan(got_g[1, p // 2])
+            assert _same_bits(np.ascontiguousarray(got_g[keep]), want_g) and _same_bits(np.ascontiguousarray(got_s[keep]), want_s)
 
 
 # ---------------------------------------------------------------------------------------------- engines
