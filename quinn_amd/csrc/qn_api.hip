@@ -618,12 +618,14 @@ __global__ __launch_bounds__(KLB) void k_vi_sample_kl(const double* __restrict__
     for (int64_t i = threadIdx.x; i < p; i += KLB) {
         const double m = mu[i], r = rho[i], e = eps[(int64_t)s * p + i];
         const double sig = exp(r);
-        const double w = m + sig * e;
+        // rounded operations per element (n_ops of tests/test_gpu_elementwise_kernels.py; an exp / log / sqrt call counts 2 = 1 ulp):
+        const double w = m + sig * e;                               // W_out: exp, mul, add = 4
         Wout[(int64_t)s * p + i] = (T)w;
-        const double dq = w - m;
-        aq += -kLogSqrt2Pi - r - (dq * dq) / (2.0 * (sig * sig));   // log(exp(r)) == r
+        const double dq = w - m;                                    // 4 + 1, twice below (squared) = 10
+        aq += -kLogSqrt2Pi - r - (dq * dq) / (2.0 * (sig * sig));   // log(exp(r)) == r; + mul, sig^2 (exp twice, mul: 5), div, 2 sub: logq 19
+        // a log density: w twice (8), w*w, var2, div, log_s (2), 2 sub = 15 (absolute, in the exponent); both: a weighted mean, 15
         const double p1 = exp(normal_logpdf(w, v1, l1)), p2 = exp(normal_logpdf(w, v2, l2));
-        ap += log(pi * p1 + (1.0 - pi) * p2);
+        ap += log(pi * p1 + (1.0 - pi) * p2);                       // + exp, mul, 1 - pi, mul, add, log: logp 23
     }
     aq = wave_sum(aq);
     ap = wave_sum(ap);
@@ -654,10 +656,12 @@ __global__ __launch_bounds__(BLK) void k_vi_grad(const double* __restrict__ mu, 
         gm += g;
         gr += g * sig * e;
         const double p1 = pi * exp(normal_logpdf(w, v1, l1)), p2 = (1.0 - pi) * exp(normal_logpdf(w, v2, l2));
+        // gp: the log densities (15, see k_vi_sample_kl) + exp (2), weight mul, w (4), s*s, div, mul, add, p1 + p2, div = 28
         const double gp = (p1 * (-w / (s1 * s1)) + p2 * (-w / (s2 * s2))) / (p1 + p2);
         pm += gp;
-        pr += gp * sig * e;
+        pr += gp * sig * e;                                         // + sig (2), 2 mul = 32; gr above: g (1) + sig (2) + 2 mul
     }
+    // S adds per accumulator; / S, kl_scale *, 1.0 +, gm - : n_ops = 36 + S covers drho (32 + S adds + 4) and dmu
     dmu[i] = gm - kl_scale * (pm / S);
     drho[i] = gr - kl_scale * (1.0 + pr / S);
 }
@@ -675,13 +679,13 @@ __global__ __launch_bounds__(BLK) void k_adam(double* __restrict__ W, const T* _
         const int64_t k = (int64_t)b * p + i;
         double w = W[k];
         double g = (double)G[k] * gscale;
-        if (wd != 0.0) g = g + wd * w;
+        if (wd != 0.0) g = g + wd * w;                   // rounded operations (n_ops of the tests): g 3
         double mm = m[k];
-        mm = mm + (1.0 - b1) * (g - mm);                 // lerp_(grad, 1-beta1), weight < 0.5 branch
+        mm = mm + (1.0 - b1) * (g - mm);                 // lerp_(grad, 1-beta1), weight < 0.5 branch.  m: 3 + sub, mul, add = 6
         double vv = v[k] * b2;
-        vv = vv + ((1.0 - b2) * g) * g;                  // addcmul_(grad, grad, value=1-beta2)
-        const double denom = sqrt(vv) / bc2_sqrt + eps;
-        w = w + (-step_size) * (mm / denom);             // addcdiv_(exp_avg, denom, value=-step_size)
+        vv = vv + ((1.0 - b2) * g) * g;                  // addcmul_(grad, grad, value=1-beta2).  v: mul, g twice (6), 2 mul, add = 10
+        const double denom = sqrt(vv) / bc2_sqrt + eps;  // 10 / 2 + sqrt (2), div, add = 9
+        w = w + (-step_size) * (mm / denom);             // addcdiv_(exp_avg, denom, value=-step_size).  W: 6 + 9 + div, mul, add = 18
         W[k] = w;
         m[k] = mm;
         v[k] = vv;
@@ -816,13 +820,13 @@ __global__ __launch_bounds__(256) void k_pred_moments(const T* __restrict__ Y, i
     if (j >= K) return;
     double s = 0.0;
     for (int64_t m = 0; m < M; ++m) s += (double)Y[m * K + j];
-    const double mu = s / (double)M;
+    const double mu = s / (double)M;                     // rounded operations besides the M adds (n_ops of the tests): mean 1
     mean[j] = mu;
     if (var) {
         double q = 0.0;
         for (int64_t m = 0; m < M; ++m) {
             const double d = (double)Y[m * K + j] - mu;
-            q += d * d;
+            q += d * d;                                  // variance: sub, mul, and the division below = 3
         }
         var[j] = q / (double)(M - 1);
     }

@@ -70,6 +70,12 @@ class DeviceAMCMC(DeviceEngine):
                  overlap_hist=True, hist_scale0=256.0, pause_gc=True, priorsigma=None):
         if op.dtype != "float64":
             raise NotImplementedError("the device AMCMC engine runs the float64 operator")
+        try:
+            hs0_ok = bool(np.isfinite(hist_scale0)) and hist_scale0 > 0
+        except TypeError:
+            hs0_ok = False
+        if not hs0_ok:                                      # (0, a negative number, NaN or inf: a NaN scale of the history rows)
+            raise ValueError("hist_scale0 must be a finite number > 0, got %r" % (hist_scale0,))
         # groups > 1: a group's accept / propose kernel (a chain of memory round trips that leaves the GPU idle: 8.7 of a step's
         # 84 us at cfg2) overlaps the other group's forward kernel.  None: 2 groups from 32 chains on (measured at cfg2: 11.9 ->
         # 12.4 k steps/s before the first adaptation; 4 groups are bound by the enqueuing thread) when the fused kernels run the

@@ -111,6 +111,20 @@ def test_compute_entry_points_reject_bad_arguments(L):
     assert L.qn_mlp_desc_destroy(d) == 0
 
 
+@pytest.mark.parametrize("bad", [0, 0.0, -256.0, float("nan"), float("inf"), -float("inf"), None, "256"])
+def test_device_amcmc_rejects_a_hist_scale0_that_is_not_finite_and_positive(bad):
+    """DeviceAMCMC(hist_scale0=...) rounds the value to a power of two through log2: a value that is not a finite number > 0
+    is a ValueError that names the argument, raised in the constructor before anything is asked of the operator but its dtype
+    (so a stub with only `dtype` does: no GPU)."""
+    from quinn_amd.mcmc.device_amcmc import DeviceAMCMC
+
+    class Op:
+        dtype = "float64"
+
+    with pytest.raises(ValueError, match="hist_scale0"):
+        DeviceAMCMC(Op(), 0.1, hist_scale0=bad)
+
+
 def test_sse_workspace_sizes_unchanged(L):
     """qn_workspace_bytes (forward and gradient) and qn_mlp_sse_parts return what tests/golden/g18_sse_workspace_bytes.json
     records for one network per kernel family of the core operator: the numbers of the library before each family's size query
