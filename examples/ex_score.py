@@ -3,7 +3,9 @@
 Kronecker-factored Laplace approximation (its weight draws and its closed-form linearised predictive).
 
 `score` draws the solver's predictive ensemble once and reduces it on the device to lppd / WAIC, PIT coverage and the
-CRPS (`quinn_amd.scoring`); lower nlpd and crps are better, and coverage[0.9] should be near 0.9."""
+CRPS (`quinn_amd.scoring`); lower nlpd and crps are better, and coverage[0.9] should be near 0.9.  On the training rows
+`loo=True` adds PSIS-LOO: `elpd_loo` estimates what `elpd_waic` does, and `n_khat_bad` counts the rows on which the
+importance weights are too heavy-tailed for either to be trusted."""
 import os
 import sys
 
@@ -22,6 +24,11 @@ NOISE = 0.1
 def line(name, s):
     cov = "  ".join(f"cov{int(100 * k)}={v:.2f}" for k, v in s["coverage"].items())
     print(f"{name:<22} nlpd={s['nlpd']:8.3f}  crps={s['crps']:.4f}  rmse={s['rmse']:.4f}  p_waic={s['p_waic']:8.2f}  {cov}")
+
+
+def loo_line(name, s):
+    print(f"{name:<22} elpd_waic={s['elpd_waic']:9.2f}  elpd_loo={s['elpd_loo']:9.2f}  p_loo={s['p_loo']:7.2f}  "
+          f"n_khat_bad={s['n_khat_bad']}/{s['n']} (khat > {s['khat_threshold']:.2f})")
 
 
 def main():
@@ -48,6 +55,10 @@ def main():
     line("Laplace kron, draws", la.score(xtst, ytst, nsam=100))
     line("Laplace kron, score_glm", la.score_glm(xtst, ytst))
     line("HMC on training (WAIC)", hmc.score(xtrn, ytrn, nsam=100, nburn=200, chain='all'))
+    print("training rows, WAIC beside PSIS-LOO:")
+    loo_line("HMC (4 chains)", hmc.score(xtrn, ytrn, nsam=100, nburn=200, chain='all', loo=True))
+    loo_line("deep ensemble (8)", ens.score(xtrn, ytrn, noise=NOISE, loo=True))
+    loo_line("Laplace kron, draws", la.score(xtrn, ytrn, nsam=100, loo=True))
 
 
 if __name__ == "__main__":

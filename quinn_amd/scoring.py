@@ -5,14 +5,17 @@ N(f_mk, noise^2 + V_mk) for entry k, the predictive is the equal-weight mixture 
 turns that `[6, K]` array into the scalar scores on the host.  On training data `waic` is the WAIC (Gelman, Hwang &
 Vehtari, Stat. Comput. 24, 2014, p_waic2); on held-out data `nlpd` is the test negative log predictive density.  The CRPS
 of a Gaussian mixture is the closed form of Grimit et al. (Q. J. R. Meteorol. Soc. 132, 2006); its pair term costs
-O(M^2 K) evaluations.  PSIS-LOO, rank histograms and energy scores across outputs are out of scope.  The reference has no
-counterpart; the per-entry definitions are in include/quinn_amd.h at `qn_pred_score`.
+O(M^2 K) evaluations.  With loo=True a second device call (`qn_psis_loo`, csrc/qn_psis.hip) adds the Pareto-smoothed
+importance-sampling leave-one-out scores: `elpd_loo`, the per-entry `khat` that says where it can be trusted, and the LOO-PIT
+(`psis.py` is their contract in numpy).  Rank histograms and energy scores across outputs are out of scope.  The reference
+has no counterpart; the per-entry definitions are in include/quinn_amd.h at `qn_pred_score` and in include/quinn_amd_psis.h at `qn_psis_loo`.
 """
 
 import numpy as np
 import torch
 
 from . import _lib
+from .psis import summarise_loo  # noqa: F401  (re-exported)
 
 ROWS = ("lppd_k", "p_waic_k", "pit", "crps_k", "mean", "var")          # the rows of qn_pred_score's output, in order
 DEFAULT_LEVELS = (0.5, 0.9, 0.95)
@@ -72,6 +75,37 @@ def score_rows(F, y, noise, V=None, what=WHAT_ALL):
     return out
 
 
+def psis_rows(F, y, noise, V=None):
+    """`qn_psis_loo` on device tensors: F `(M, K)` float64 / float32 contiguous, V the same or None, y `(K,)` float64
+    -> `[4, K]` float64 device tensor (elpd_loo_k, khat, ess_k, pit_loo)."""
+    M, K = F.shape
+    L = _lib.lib()
+    need = int(L.qn_psis_loo_workspace_bytes(M, K))
+    if need == 0:
+        raise ValueError(L.qn_last_error().decode())
+    if V is not None and (V.shape != F.shape or V.dtype != F.dtype or V.device != F.device):
+        raise ValueError("V must match F in shape, dtype and device")
+    if y.shape != (K,) or y.dtype != torch.float64 or y.device != F.device:
+        raise ValueError(f"y: a float64 tensor of {K} entries on F's device is needed")
+    out = torch.empty((_lib.LOO_NOUT, K), dtype=torch.float64, device=F.device)
+    ws = torch.empty(need // 8, dtype=torch.float64, device=F.device)
+    qdt = _lib.QN_F32 if F.dtype == torch.float32 else _lib.QN_F64
+    with torch.cuda.device(F.device):
+        st = _lib.stream(F.device)
+        _lib.check(L.qn_psis_loo(F.data_ptr(), V.data_ptr() if V is not None else None, qdt, y.data_ptr(), M, K,
+                                 float(noise), out.data_ptr(), ws.data_ptr(), need, st), "qn_psis_loo")
+    return out
+
+
+def summarise_all(rows, loo_rows, y, M, levels=DEFAULT_LEVELS):
+    """`summarise(rows, y)`, and with `loo_rows` (the `[4, K]` rows of `qn_psis_loo`, or None) the keys of `summarise_loo`
+    and `p_loo` = lppd - elpd_loo beside them."""
+    res = summarise(rows, y, levels)
+    if loo_rows is not None:
+        res.update(summarise_loo(loo_rows, y, M, lppd=res["lppd"], levels=levels))
+    return res
+
+
 def _ens_tensor(a, K, device, name):
     """`(M, K)` contiguous float64 / float32 device tensor of an `(M, N, o)` or `(M, K)` ensemble array."""
     t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
@@ -82,11 +116,12 @@ def _ens_tensor(a, K, device, name):
     return t.to(device).reshape(t.shape[0], K).contiguous()
 
 
-def pred_score(F, y, noise, V=None, crps=True, levels=DEFAULT_LEVELS, device=None):
+def pred_score(F, y, noise, V=None, crps=True, levels=DEFAULT_LEVELS, device=None, loo=False):
     """Score the predictive ensemble F `(M, N, o)` or `(M, K)` (device tensor or numpy; float32 is read as it is, all
     arithmetic is float64) against the targets y `(N, o)` / `(K,)`: member m predicts N(F[m], noise^2 + V[m]), V an optional
     per-member predictive variance shaped like F.  Returns the dict of `summarise`.  crps=False skips the O(M^2 K) pair pass
-    (`crps_k` and `crps` are NaN).  Only the `6 x K` result leaves the device."""
+    (`crps_k` and `crps` are NaN).  loo=True adds the PSIS-LOO keys of `summarise_loo` and `p_loo` (one more device call).
+    Only the `6 x K` (with loo, `10 x K`) result leaves the device."""
     y = np.asarray(y, dtype=np.float64)
     if isinstance(F, torch.Tensor) and F.is_cuda:
         dev = F.device
@@ -96,4 +131,5 @@ def pred_score(F, y, noise, V=None, crps=True, levels=DEFAULT_LEVELS, device=Non
     Vt = None if V is None else _ens_tensor(V, y.size, dev, "V").to(Ft.dtype)
     what = WHAT_ALL if crps else WHAT_ALL & ~_lib.SCORE_CRPS
     yt = torch.as_tensor(y.reshape(-1), device=dev)
-    return summarise(score_rows(Ft, yt, noise, Vt, what).cpu().numpy(), y, levels)
+    loo_rows = psis_rows(Ft, yt, noise, Vt).cpu().numpy() if loo else None
+    return summarise_all(score_rows(Ft, yt, noise, Vt, what).cpu().numpy(), loo_rows, y, Ft.shape[0], levels)

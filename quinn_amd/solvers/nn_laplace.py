@@ -354,11 +354,12 @@ class NN_Laplace(NN_RMS):
                           "semi-definite); values are not clipped.", RuntimeWarning)
         return mean, (var if msc >= 1 else None), (cov if msc == 2 else None)
 
-    def score_glm(self, x, y, noise=None, crps=True, levels=scoring.DEFAULT_LEVELS):
+    def score_glm(self, x, y, noise=None, crps=True, levels=scoring.DEFAULT_LEVELS, loo=False):
         """Score the closed-form linearised predictive against the targets y `(N, o)` at x: the dict of `QUiNNBase.score`, with
         member b predicting N(f_b(x_n)_k, noise^2 + (J_n Sigma_b J_n^T)_kk) per entry -- the members' means and the diagonal of
         their predictive covariances go to `qn_pred_score` as F and V.  No weight draws; `noise` defaults to `datanoise`.
-        With la_type 'full' a negative predictive variance makes that entry's scores NaN."""
+        With la_type 'full' a negative predictive variance makes that entry's scores NaN.  loo=True adds the PSIS-LOO keys, as
+        in `QUiNNBase.score`."""
         sigma = self._score_noise(noise)
         y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
         f, S = self._glm_members(x)
@@ -366,5 +367,6 @@ class NN_Laplace(NN_RMS):
         V = torch.diagonal(S, dim1=-2, dim2=-1).contiguous()
         what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
         yt = torch.as_tensor(y.reshape(-1), device=f.device)
-        rows = scoring.score_rows(f.contiguous().reshape(M, -1), yt, sigma, V.reshape(M, -1), what)
-        return scoring.summarise(rows.cpu().numpy(), y, levels)
+        F, V = f.contiguous().reshape(M, -1), V.reshape(M, -1)
+        loo_rows = scoring.psis_rows(F, yt, sigma, V).cpu().numpy() if loo else None
+        return scoring.summarise_all(scoring.score_rows(F, yt, sigma, V, what).cpu().numpy(), loo_rows, y, M, levels)

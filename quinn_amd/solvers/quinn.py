@@ -157,7 +157,8 @@ class QUiNNBase():
         the noise level and `noise` is None; else None (one level for all members: `_score_noise`)."""
         return None
 
-    def score(self, x, y, noise=None, nsam=1000, crps=True, max_bytes=256 << 20, levels=scoring.DEFAULT_LEVELS, **ens_args):
+    def score(self, x, y, noise=None, nsam=1000, crps=True, max_bytes=256 << 20, levels=scoring.DEFAULT_LEVELS, loo=False,
+              **ens_args):
         """Score the solver's `nsam`-member predictive ensemble against the targets y `(N, o)` at x: the dict of
         `scoring.summarise` (per entry lppd_k, p_waic_k, pit, crps_k, mean, var; scalars lppd, p_waic, elpd_waic, waic,
         se_elpd, nlpd, crps, rmse, coverage, pit_hist).  Member m predicts N(f_m(x), noise^2); `noise` defaults to the data
@@ -166,7 +167,10 @@ class QUiNNBase():
         `nburn`, `chain='all'`; a solver that sampled the noise level scores member m at its own level, through the
         per-member variance V of `qn_pred_score`, unless `noise` is given), then x is walked in row chunks whose `M x rows x o` predictions fit `max_bytes`: one batched
         forward and one `qn_pred_score` per chunk, and only `6 x rows x o` doubles are downloaded.  An entry's scores do
-        not depend on the chunking.  crps=False skips the pair pass, which costs O(M^2) per entry."""
+        not depend on the chunking.  crps=False skips the pair pass, which costs O(M^2) per entry.  loo=True adds the
+        PSIS-LOO scores (`scoring.summarise_loo`: elpd_loo_k, khat, ess_k, pit_loo, elpd_loo, looic, se_elpd_loo, khat_threshold,
+        n_khat_bad, khat_bad, coverage_loo, pit_loo_hist; and p_loo): one `qn_psis_loo` per chunk on the same F and V and
+        `4 x rows x o` more doubles downloaded."""
         member = self._score_member_noise(noise, nsam, **ens_args)
         sigma = self._score_noise(noise) if member is None else 0.0
         x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
@@ -177,6 +181,7 @@ class QUiNNBase():
         step = max(1, int(max_bytes) // (M * o * esize))
         what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
         rows = np.empty((_lib.SCORE_NOUT, N * o))
+        loo_rows = np.empty((_lib.LOO_NOUT, N * o)) if loo else None
         for lo in range(0, N, step):
             hi = min(N, lo + step)
             F = self._predict_batch_dev(W, x[lo:hi]).contiguous()
@@ -186,7 +191,9 @@ class QUiNNBase():
             F = F.reshape(M, -1)
             V = None if member is None else (torch.as_tensor(member, device=F.device) ** 2).to(F.dtype)[:, None].expand_as(F).contiguous()
             rows[:, lo * o:hi * o] = scoring.score_rows(F, yt, sigma, V, what).cpu().numpy()
-        return scoring.summarise(rows, y, levels)
+            if loo:
+                loo_rows[:, lo * o:hi * o] = scoring.psis_rows(F, yt, sigma, V).cpu().numpy()
+        return scoring.summarise_all(rows, loo_rows, y, M, levels)
 
     # -- figures (presentation only; same signatures and file names as quinn.py:106-260) ---------------
     @staticmethod
