@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|stack|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -13,6 +13,8 @@ prints its closed-form linearised predictive (`predict_glm`) beside the sampled 
 `laplace_kron` is the same with the Kronecker-factored Gauss-Newton (`la_type='kron'`: two small factors per layer, no p x p matrix),
 `sghmc` is the device-only stochastic-gradient HMC (`engine='device'`; every chain draws its own minibatch on the GPU, cyclical
 step size, every 10th state stored; MLP network),
+`stack` is the device HMC (`engine='device'`; MLP network) whose 8 chains are stacked (`NN_MCMC.stack`: PSIS-LOO density per chain,
+EM for the weights on the device) and scored on the test rows with equal and with stacking weights,
 `pt` is the device HMC with replica exchange (`engine='device'`, 8 ladders of 4 rungs; predictions and diagnostics from the cold
 chains; MLP network),
 `prior` is the device HMC with the Gaussian weight prior `priorsigma=1.0` (`engine='device'`; MLP network), printed beside the same
@@ -50,7 +52,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
@@ -59,7 +61,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'stack', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -79,6 +81,23 @@ def main(meth, quick=False, mlp=False):
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc',
                   sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True)
         predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
+    elif meth == 'stack':
+        # 8 device HMC chains from different seeds; they do not mix, so they are stacked instead of pooled with equal weights
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                  sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True)
+        ens = dict(nsam=100 // k * 8, nburn=1000 // k)
+        predict = lambda x: uqnet.predict_ens(x, nens=ens['nsam'], nburn=ens['nburn'], chain='all')
+        st = uqnet.stack(xtrn, ytrn, loo=True, **ens)
+        print("  stacking weights of the chains:", np.round(st['weights'], 4), f"({st['iters']} EM iterations, gap {st['gap']:.1e} nats)")
+        print(f"  elpd_loo of the stacked mixture {st['elpd_stack']:.3f}, of the equal-weight pool {st['elpd_equal']:.3f}; "
+              f"share of entries with an unreliable khat per chain: {np.round(st['khat_bad_share'], 2)}")
+        for label, wm in (('equal weights', None), ('stacked', st['member_weights'])):
+            sc = uqnet.score(xtst, ytst, chain='all', member_weights=wm, **ens)
+            print(f"  test scores, {label}: nlpd {sc['nlpd']:.3f}  crps {sc['crps']:.4f}  rmse {sc['rmse']:.4f}  "
+                  f"90 % coverage {sc['coverage'][0.9]:.2f}")
+        sm, sv = uqnet.predict_mom_stacked(xtst)
+        print(f"  stacked predictive on the test rows: mean |mean - y| {np.mean(np.abs(sm - ytst)):.4f}, mean std {np.mean(np.sqrt(sv)):.4f}")
     elif meth == 'pt':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
@@ -199,7 +218,7 @@ def main(meth, quick=False, mlp=False):
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
         if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
-    if meth in ('amcmc', 'hmc', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts'):
+    if meth in ('amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])
         for name, label in (('params', 'parameters'), ('logpost', 'log-posterior'), ('pred', 'predictions on the grid')):
             d = dg[name]

@@ -15,6 +15,7 @@ from ..ens.learner import Learner
 from ..nns.nnfit import fit_members, load_flat_into, draw_perms
 from ..parallel import shard_bounds, all_gather_rows, dist_info
 from ..ops import flatten_module
+from .. import scoring
 from .quinn import QUiNNBase
 
 
@@ -83,6 +84,24 @@ class NN_Ens(QUiNNBase):
             nens = self.nens
         order = np.random.permutation(nens)
         return self._best_w[order]
+
+    def _ens_weights_ordered(self, nens=None):
+        """The first `nens` members in their own order (`_ens_weights` shuffles them)."""
+        return self._best_w[:self.nens if nens is None else min(nens, self.nens)]
+
+    def stack(self, x, y, noise=None, loo=False, tol=scoring.DEFAULT_TOL, max_iter=scoring.DEFAULT_MAX_ITER, max_bytes=256 << 20):
+        """Classic stacking of the ensemble members on HELD-OUT data (x, y) (Yao, Vehtari, Simpson & Gelman 2018): the
+        weights on the simplex that maximise the log density of sum_j w_j N(f_j(x), noise^2) there (`qn_group_lpd` with
+        groups of one member, `qn_stack_weights`); an untrained or diverged member gets a weight near 0 instead of 1 / nens.
+        A member is one weight vector, which has no leave-one-out density: loo=True is refused.  Returns and stores as
+        `self.stacking` the dict of `NN_MCMC.stack` (`weights` and `member_weights` coincide, `khat_bad_share` is None); use it
+        as `score(x, y, nsam=nens, member_weights=...)` and `predict_mom_stacked(x)`."""
+        if loo:
+            raise ValueError("NN_Ens.stack works on held-out data only: a member is a single weight vector (loo=True is refused)")
+        W = self._ens_weights_ordered()
+        res = self._stack_groups(x, y, W, np.arange(len(W) + 1), None, self._score_noise(noise), False, tol, max_iter, max_bytes)
+        res.update(nsam=len(W), ens_args={})
+        return res
 
     def _predict_ens_dev(self, x, nens=None):
         return self._predict_batch_dev(self._ens_weights(nens), x)

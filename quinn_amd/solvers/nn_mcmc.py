@@ -34,6 +34,7 @@ from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
 from ..mcmc.hyper import check_hyperprior, group_segments, initial_tau
 from ..mcmc.noise import check_noiseprior
+from .. import scoring
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
 from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
@@ -548,6 +549,33 @@ class NN_MCMC(QUiNNBase):
         if noise is None and getattr(self, 'lpinfo', None) and self.lpinfo['lparams'].get('noiseprior') is not None:
             return self.noise_samples(nsam, **ens_args)
         return None
+
+    def stack(self, x, y, nsam=1000, nburn=1000, loo=True, noise=None, tol=scoring.DEFAULT_TOL, max_iter=scoring.DEFAULT_MAX_ITER,
+              max_bytes=256 << 20):
+        """Stacking weights of the chains (Yao, Vehtari & Gelman 2022): chains that did not mix are not pooled with equal
+        weights but with the weights on the simplex that maximise the log predictive density of the weighted mixture on
+        (x, y).  The groups are the chains of `chain='all'` (the cold chains after a ladder fit), chain c with its nsam // C +
+        (c < nsam % C) thinned draws.  loo=True (x, y the training data): a chain's density of an entry is its PSIS-LOO
+        density (`qn_psis_loo` per chain; at least 2 draws per chain); loo=False (held-out data): its plain predictive density
+        (`qn_group_lpd`).  x is walked in the row chunks of `score`, the `[C, N * o]` matrix stays on the device, and
+        `qn_stack_weights` iterates EM to a certified gap of `tol` nats.  A sampled noise level goes through V as in `score`.
+        Returns and stores as `self.stacking`: `weights` `(C,)`, `member_weights` `(M,)` (for `score(member_weights=...)`
+        and `predict_mom_stacked`, with the same nsam, nburn and chain='all'), `elpd_stack` and `elpd_equal` (the objective at
+        the weights and at 1 / C), `gap`, `iters`, `n_dropped`, `n_nonfinite`, `khat_bad_share` `(C,)` (loo only: the share
+        of entries whose khat is above the threshold, per chain), `offsets`, `nsam`, `ens_args`."""
+        if self.samples is None or np.ndim(self.samples) != 3:
+            raise ValueError("stack needs the stored chains of a multi-chain fit")
+        maxpost = np.atleast_1d(self.mcmc_results.get('maxpost', np.empty(self.samples.shape[0])))      # gathered from every rank
+        if len(maxpost) != self.samples.shape[0]:
+            raise ValueError("this rank does not hold every chain (gather_chain='none' across ranks): stack needs them all")
+        ens_args = dict(nburn=nburn, chain='all')
+        picks = self._ens_picks(nsam, nburn, 'all')
+        offsets = np.concatenate([[0], np.cumsum([len(rows) for _, rows in picks])])
+        member = self._score_member_noise(noise, nsam, **ens_args)
+        sigma = self._score_noise(noise) if member is None else 0.0
+        res = self._stack_groups(x, y, self._ens_weights(nsam, **ens_args), offsets, member, sigma, loo, tol, max_iter, max_bytes)
+        res.update(nsam=nsam, ens_args=ens_args)
+        return res
 
     def _predict_ens_dev(self, x, nens=10, nburn=1000, chain=0):
         return self._predict_batch_dev(self._ens_weights(nens, nburn, chain), x)

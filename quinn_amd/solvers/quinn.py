@@ -157,8 +157,69 @@ class QUiNNBase():
         the noise level and `noise` is None; else None (one level for all members: `_score_noise`)."""
         return None
 
+    def _ens_weights_ordered(self, nens=None, **ens_args):
+        """`_ens_weights` in an order that two calls reproduce, for per-member weights; a solver whose `_ens_weights` shuffles
+        the members overrides this."""
+        return self._ens_weights(nens, **ens_args)
+
+    def _score_chunks(self, W, x, y, member, max_bytes):
+        """(lo, hi, F `(M, rows * o)`, y chunk or None, V or None) over the row chunks of `score` (y `(N, o)` or None)."""
+        M, N, o = len(W), len(x), (self.arch.dims[-1] if y is None else y.shape[1])
+        esize = 4 if self._dtype == "float32" else 8
+        step = max(1, int(max_bytes) // (M * o * esize))
+        for lo in range(0, N, step):
+            hi = min(N, lo + step)
+            F = self._predict_batch_dev(W, x[lo:hi]).contiguous()
+            if F.dtype not in (torch.float32, torch.float64):
+                F = F.double()
+            yt = None if y is None else torch.as_tensor(y[lo:hi].reshape(-1), device=F.device)
+            F = F.reshape(M, -1)
+            V = None if member is None else (torch.as_tensor(member, device=F.device) ** 2).to(F.dtype)[:, None].expand_as(F).contiguous()
+            yield lo, hi, F, yt, V
+
+    def _stack_groups(self, x, y, W, offsets, member, sigma, loo, tol, max_iter, max_bytes):
+        """The stacking of the groups offsets[g] .. offsets[g + 1] - 1 of the weight vectors W `(M, p)` on the data (x, y): L
+        `[G, N * o]` is assembled on the device over the row chunks of `score` (`scoring.group_lpd`), `scoring.stack_weights`
+        optimises, and the dict documented at `NN_MCMC.stack` is stored as `self.stacking` and returned."""
+        from .. import stacking
+        x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
+        y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
+        N, o = y.shape
+        G = len(offsets) - 1
+        L, bad = None, np.zeros(G)
+        for lo, hi, F, yt, V in self._score_chunks(W, x, y, member, max_bytes):
+            if L is None:
+                L = torch.empty((G, N * o), dtype=torch.float64, device=F.device)
+            Lc, share = scoring.group_lpd(F, yt, sigma, offsets, V, loo=loo)
+            L[:, lo * o:hi * o] = Lc
+            if loo:
+                bad += share * (hi - lo) / N
+        res = scoring.stack_weights(L, tol=tol, max_iter=max_iter)
+        self.stacking = {"weights": res["w"], "member_weights": stacking.member_weights(res["w"], offsets),
+                         "elpd_stack": res["obj"], "elpd_equal": res["obj_equal"], "gap": res["gap"], "iters": res["iters"],
+                         "n_dropped": res["n_dropped"], "n_nonfinite": res["n_nonfinite"],
+                         "khat_bad_share": bad if loo else None, "offsets": np.asarray(offsets, dtype=np.int64)}
+        return self.stacking
+
+    def predict_mom_stacked(self, x, stacking=None, max_bytes=256 << 20):
+        """(mean `(N, o)`, variance `(N, o)`) of the stacked predictive sum_m wm_m delta(f_m(x)) -- the weighted mean and the
+        weighted variance sum wm (f - mean)^2 / (1 - sum wm^2) of the member predictions, without the data noise -- from
+        MOMENTS-only calls of `qn_pred_score_w` on the members `stack` weighted (`stacking`: its dict; default the last one)."""
+        stacking = self.stacking if stacking is None else stacking
+        x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
+        W = self._ens_weights_ordered(stacking["nsam"], **stacking["ens_args"])
+        wm = None
+        mean, var = [], []
+        for lo, hi, F, _, _ in self._score_chunks(W, x, None, None, max_bytes):
+            if wm is None:
+                wm = torch.as_tensor(np.asarray(stacking["member_weights"], dtype=np.float64), device=F.device)
+            rows = scoring.score_rows_w(F, None, 0.0, wm, None, _lib.SCORE_MOMENTS).cpu().numpy()
+            mean.append(rows[4].reshape(hi - lo, -1))
+            var.append(rows[5].reshape(hi - lo, -1))
+        return np.concatenate(mean), np.concatenate(var)
+
     def score(self, x, y, noise=None, nsam=1000, crps=True, max_bytes=256 << 20, levels=scoring.DEFAULT_LEVELS, loo=False,
-              **ens_args):
+              member_weights=None, **ens_args):
         """Score the solver's `nsam`-member predictive ensemble against the targets y `(N, o)` at x: the dict of
         `scoring.summarise` (per entry lppd_k, p_waic_k, pit, crps_k, mean, var; scalars lppd, p_waic, elpd_waic, waic,
         se_elpd, nlpd, crps, rmse, coverage, pit_hist).  Member m predicts N(f_m(x), noise^2); `noise` defaults to the data
@@ -170,26 +231,30 @@ class QUiNNBase():
         not depend on the chunking.  crps=False skips the pair pass, which costs O(M^2) per entry.  loo=True adds the
         PSIS-LOO scores (`scoring.summarise_loo`: elpd_loo_k, khat, ess_k, pit_loo, elpd_loo, looic, se_elpd_loo, khat_threshold,
         n_khat_bad, khat_bad, coverage_loo, pit_loo_hist; and p_loo): one `qn_psis_loo` per chunk on the same F and V and
-        `4 x rows x o` more doubles downloaded."""
+        `4 x rows x o` more doubles downloaded.  member_weights `(M,)` (>= 0, sum 1: `stack(...)['member_weights']`, with the
+        nsam and ens_args `stack` was called with) scores the weighted mixture through `qn_pred_score_w` instead of the
+        equal-weight one; the members then come in the reproducible order of `_ens_weights_ordered`.  Not together with loo."""
+        if member_weights is not None and loo:
+            raise ValueError("loo=True scores the equal-weight ensemble: not together with member_weights")
         member = self._score_member_noise(noise, nsam, **ens_args)
         sigma = self._score_noise(noise) if member is None else 0.0
         x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
         y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
-        W = self._ens_weights(nsam, **ens_args)
+        W = self._ens_weights(nsam, **ens_args) if member_weights is None else self._ens_weights_ordered(nsam, **ens_args)
         M, (N, o) = len(W), y.shape
-        esize = 4 if self._dtype == "float32" else 8
-        step = max(1, int(max_bytes) // (M * o * esize))
         what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
         rows = np.empty((_lib.SCORE_NOUT, N * o))
         loo_rows = np.empty((_lib.LOO_NOUT, N * o)) if loo else None
-        for lo in range(0, N, step):
-            hi = min(N, lo + step)
-            F = self._predict_batch_dev(W, x[lo:hi]).contiguous()
-            if F.dtype not in (torch.float32, torch.float64):
-                F = F.double()
-            yt = torch.as_tensor(y[lo:hi].reshape(-1), device=F.device)
-            F = F.reshape(M, -1)
-            V = None if member is None else (torch.as_tensor(member, device=F.device) ** 2).to(F.dtype)[:, None].expand_as(F).contiguous()
+        wm = None
+        if member_weights is not None:
+            wm = np.asarray(member_weights, dtype=np.float64).reshape(-1)
+            if wm.shape != (M,):
+                raise ValueError(f"member_weights holds {wm.size} weights for an ensemble of {M} members")
+        for lo, hi, F, yt, V in self._score_chunks(W, x, y, member, max_bytes):
+            if wm is not None:
+                wm = torch.as_tensor(wm, device=F.device)
+                rows[:, lo * o:hi * o] = scoring.score_rows_w(F, yt, sigma, wm, V, what).cpu().numpy()
+                continue
             rows[:, lo * o:hi * o] = scoring.score_rows(F, yt, sigma, V, what).cpu().numpy()
             if loo:
                 loo_rows[:, lo * o:hi * o] = scoring.psis_rows(F, yt, sigma, V).cpu().numpy()
