@@ -8,7 +8,8 @@ diagnostics: weight-space R-hat of a neural network is pessimistic, hidden units
 Definitions: classic split-R-hat (Gelman et al., Bayesian Data Analysis, 3rd ed., section 11.4) over the m = 2C half
 chains, and the batch-means estimate of the effective sample size (Flegal & Jones, Ann. Statist. 38, 2010) with batches
 of floor(sqrt(n)) draws.  Both need one pass and neither a sort nor an FFT.  Rank-normalised / folded R-hat (Vehtari et
-al. 2021) and autocorrelation-based ESS are out of scope.  The reference runs one chain and has no counterpart.
+al. 2021) and autocorrelation-based ESS are in `rankdiag.py` (`qn_rank_diag`, csrc/qn_rank.hip), which sorts the pooled
+draws of every entry.  The reference runs one chain and has no counterpart.
 """
 import math
 

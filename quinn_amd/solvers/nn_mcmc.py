@@ -30,6 +30,7 @@ from ..mcmc.ess import check_ess_args
 from ..mcmc.device_nuts import DeviceNUTS
 from ..mcmc.nuts import check_nuts_args
 from ..mcmc import diagnostics as diag
+from ..mcmc import rankdiag
 from ..mcmc.tempering import check_temper_args, check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
 from ..mcmc.hyper import check_hyperprior, group_segments, initial_tau
@@ -44,6 +45,12 @@ DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 's
                   'ess': DeviceESS, 'nuts': DeviceNUTS}
 # stochastic-gradient samplers, elliptical slice sampling, the No-U-Turn sampler: no host counterpart
 DEVICE_ONLY = ('sgld', 'sghmc', 'ess', 'nuts')
+
+
+def _rank_keys(stats):
+    """The dict of `rankdiag.rank_stats` as it is merged into a diagnostics dict: the figures under their own names, the plan
+    (n_draws, nh, stride, t0) under rank_*, so that the batch plan's n_draws and t0 stay what they were."""
+    return {(f"rank_{k}" if k in ("n_draws", "nh", "stride", "t0") else k): v for k, v in stats.items()}
 
 
 class NN_MCMC(QUiNNBase):
@@ -189,6 +196,10 @@ class NN_MCMC(QUiNNBase):
             so it works with gather_chain='none'; host engines: the numpy chain is uploaded in bounded pieces.  Multi-rank:
             each rank reduces its own chains, the small per-chain statistics follow `gather`.  diag_nburn: rows discarded
             first (None: nmcmc // 2).  False (default): nothing is computed and `self.diagnostics` is None.
+            'rank' -- what True does, and the rank-normalised figures of `quinn_amd.mcmc.rankdiag.rank_stats` (rhat_bulk,
+            rhat_tail, rhat_rank, ess_bulk, ess_tail, ess_mean, mcse_mean; their plan under rank_n_draws, rank_nh, rank_stride,
+            rank_t0) merged into both dicts, from the same tensors (so also with gather_chain='none').  Ranking pools all
+            chains: with more than one rank and chains the calling rank does not hold it is a ValueError.
             sampler_params of 'hmc' / 'mala' with engine='device' may hold ladder=R (or a decreasing sequence of inverse
             temperatures starting at 1), beta_min (default 0.01) and swap_every (default 1): replica exchange
             (`quinn_amd.mcmc.tempering`).  The nchains chains are nchains / R ladders, chain c is rung c % R and samples
@@ -401,7 +412,7 @@ class NN_MCMC(QUiNNBase):
                         raise ValueError("diagnostics=True needs the stored chain")
                     cp = (lambda v: v.contiguous()) if isinstance(dch, torch.Tensor) else np.ascontiguousarray
                     dch, dlp, dtot = cp(dch[::R]), cp(dlp[::R]), ctot // R        # (a copy of 1 / R of the chain)
-                self.diagnostics = self._fit_diagnostics(dch, dlp, diag_nburn, dtot, gather)
+                self.diagnostics = self._fit_diagnostics(dch, dlp, diag_nburn, dtot, gather, rank=diagnostics == 'rank')
             # the single collective, at the end, straight from the device tensors (world == 1: a device->host copy)
             res = gather_results(res, ctot, gather, gather_chain)
             self.mcmc_results = res
@@ -438,23 +449,35 @@ class NN_MCMC(QUiNNBase):
             if sharded and ch.shape[0] == ctot:      # gathered chains: every rank reduces its own shard only
                 lo, hi = shard_bounds(ctot)
                 ch, lp = ch[lo:hi], lp[lo:hi]
-            self.diagnostics = self._fit_diagnostics(ch, lp, diag_nburn, ctot if sharded else None, gather)
+            self.diagnostics = self._fit_diagnostics(ch, lp, diag_nburn, ctot if sharded else None, gather,
+                                                     rank=diagnostics == 'rank')
 
-    def _fit_diagnostics(self, chain, lps, nburn, ctot, gather):
+    def _fit_diagnostics(self, chain, lps, nburn, ctot, gather, rank=False):
         """{'params', 'logpost'}: diagnostics of this rank's chains `[C, T, p]` and log-posterior traces `[C, T]`
-        (device tensors or numpy), the per-chain statistics gathered over the ranks as `gather` says."""
+        (device tensors or numpy), the per-chain statistics gathered over the ranks as `gather` says.  rank: the figures of
+        `rankdiag.rank_stats` are merged in (they pool the chains, so every chain must be here)."""
         if chain is None:
             raise ValueError("diagnostics=True needs the stored chain")
         dev = self._device
-        return {'params': diag.diagnose_chains(chain, nburn, n_total=ctot, gather=gather, device=dev),
-                'logpost': diag.diagnose_chains(lps[..., None], nburn, n_total=ctot, gather=gather, device=dev)}
+        if rank and ctot is not None and dist_info()[1] > 1 and chain.shape[0] != ctot:
+            raise ValueError(f"diagnostics='rank' ranks the pooled draws of all {ctot} chains; this rank holds {chain.shape[0]} "
+                             "(rank diagnostics across ranks are not covered)")
+        out = {'params': diag.diagnose_chains(chain, nburn, n_total=ctot, gather=gather, device=dev),
+               'logpost': diag.diagnose_chains(lps[..., None], nburn, n_total=ctot, gather=gather, device=dev)}
+        if rank:
+            for key, ch in (('params', chain), ('logpost', lps[..., None])):
+                if out[key] is not None:
+                    out[key].update(_rank_keys(rankdiag.rank_stats(ch, nburn, device=dev)))
+        return out
 
-    def diagnose(self, x=None, nburn=1000, nens=100):
+    def diagnose(self, x=None, nburn=1000, nens=100, rank=False):
         """Diagnostics of `self.samples` (`[C, T, p]`; one 2-D chain counts as C = 1) after `nburn` rows: {'params': ...}
         as `fit(diagnostics=True)` computes it.  With x `(N, d)` also FUNCTION-SPACE diagnostics under 'pred': `nens` draws
         per chain thinned by the reference's rule (rows nburn + j * int((T - nburn) / nens)), all C * nens predictions from
         one batched forward, and the same statistics over the `[C, nens, N * o]` stack; rhat / ess / mean / var there
-        have shape `(N, o)`.  Predictions, unlike weights, do not change when hidden units are permuted."""
+        have shape `(N, o)`.  Predictions, unlike weights, do not change when hidden units are permuted.
+        rank=True merges the rank-normalised figures (`fit(diagnostics='rank')` names them) into 'params' and 'pred'; the
+        prediction figures have shape `(N, o)`."""
         samples = np.asarray(self.samples)
         if samples.ndim == 2:
             samples = samples[None]
@@ -462,6 +485,8 @@ class NN_MCMC(QUiNNBase):
         if cold is not None:
             samples = samples[cold]
         out = {'params': diag.diagnose_chains(samples, nburn, device=self._device)}
+        if rank:
+            out['params'].update(_rank_keys(rankdiag.rank_stats(samples, nburn, device=self._device)))
         if x is not None:
             C, T, p = samples.shape
             rows = diag.thinned_rows(T, nens, nburn)
@@ -472,6 +497,9 @@ class NN_MCMC(QUiNNBase):
             pred = diag.diagnose_chains(y.contiguous().view(C, nens, N * o), 0)
             for k in ('rhat', 'ess', 'mean', 'var'):
                 pred[k] = pred[k].reshape(N, o)
+            if rank:
+                rk = _rank_keys(rankdiag.rank_stats(y.contiguous().view(C, nens, N * o), 0))
+                pred.update((k, v.reshape(N, o) if isinstance(v, np.ndarray) else v) for k, v in rk.items())
             out['pred'] = pred
         return out
 
