@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|stack|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|stack|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|laplace_evidence|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -11,6 +11,8 @@ and print how well the chains agree (split-R-hat / ESS of parameters, log-poster
 `laplace_ggn` is the Laplace solver with the Gauss-Newton curvature (`la_type='ggn'`, positive definite by construction) and
 prints its closed-form linearised predictive (`predict_glm`) beside the sampled one,
 `laplace_kron` is the same with the Kronecker-factored Gauss-Newton (`la_type='kron'`: two small factors per layer, no p x p matrix),
+`laplace_evidence` is a `la_type='kron'` fit at a deliberately wrong `datanoise` followed by `tune_hyper`: it prints the members'
+log evidence before and after, the tuned scales and the held-out nlpd of `score_glm` before and after,
 `sghmc` is the device-only stochastic-gradient HMC (`engine='device'`; every chain draws its own minibatch on the GPU, cyclical
 step size, every 10th state stored; MLP network),
 `stack` is the device HMC (`engine='device'`; MLP network) whose 8 chains are stacked (`NN_MCMC.stack`: PSIS-LOO density per chain,
@@ -52,16 +54,18 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
+    if meth == 'laplace_evidence':       # the evidence's fixed point needs more entries of y than effective parameters
+        nall = 150
     domain = np.tile(np.array([-np.pi, np.pi]), (ndim, 1))
     xall = scale01ToDom(np.random.rand(nall, ndim), domain)
     yall = Sine(xall, datanoise=datanoise)
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'sghmc', 'stack', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'sghmc', 'stack', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -194,6 +198,25 @@ def main(meth, quick=False, mlp=False):
         uqnet = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='kron', datanoise=datanoise)
         uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=2, nepochs=1000 // k, freq_out=1000)
         predict = lambda x: uqnet.predict_ens(x, nens=111)
+    elif meth == 'laplace_evidence':
+        # a 'kron' fit at a deliberately wrong noise level (10 x the data's), then the noise level and the per-layer prior
+        # precisions that maximise every member's Laplace evidence at its MAP weights; the MAP weights are not refitted
+        uqnet = NN_Laplace(nnet, nens=3, dfrac=1.0, verbose=not quick, la_type='kron', datanoise=10 * datanoise)
+        uqnet.fit(xtrn, ytrn, val=[xval, yval], lrate=0.01, batch_size=15, nepochs=1000 // k, freq_out=1000)
+        nlpd_before = uqnet.score_glm(xtst, ytst)['nlpd']
+        tuned = uqnet.tune_hyper(groups='layer')
+        print("  log evidence of the members at the fit's scales:", np.round(tuned['logZ_start'], 3))
+        print("  ... and at their tuned scales:                  ", np.round(tuned['logZ'], 3),
+              f"(iterations {tuned['iters']}, converged {tuned['converged']})")
+        print(f"  datanoise of the fit {uqnet.datanoise:g}, tuned per member:", np.round(tuned['datanoise'], 4))
+        print("  prior precisions per layer, tuned per member (the fit's: %g):" % (1.0 / uqnet.priorsigma ** 2))
+        for row in tuned['prior_prec']:
+            print("   ", np.round(row, 4))
+        print("  effective number of parameters per member:", np.round(tuned['gamma'].sum(axis=1), 2), f"of {uqnet.nparams}")
+        print(f"  nlpd of the linearised predictive on the held-out rows: {nlpd_before:.4f} before, "
+              f"{uqnet.score_glm(xtst, ytst)['nlpd']:.4f} after")
+        print("  evidence weights of the members:", np.round(uqnet.evidence_weights(), 4))
+        predict = lambda x: uqnet.predict_ens(x, nens=111)
     elif meth == 'swag':
         uqnet = NN_SWAG(nnet, nens=3, dfrac=1.0, verbose=not quick, k=10, n_steps=12, c=1, cov_type="lowrank",
                         lr_swag=0.01)
@@ -210,13 +233,13 @@ def main(meth, quick=False, mlp=False):
     print(f"{meth}: {y.shape[0]} predictive samples on an 11-point grid")
     for xg, m, s, t in zip(xgrid[:, 0], ymean, ystd, np.sin(xgrid[:, 0])):
         print(f"  x={xg:+.3f}  mean={m:+.4f}  std={s:.4f}  truth={t:+.4f}")
-    if meth in ('laplace_ggn', 'laplace_kron'):
+    if meth in ('laplace_ggn', 'laplace_kron', 'laplace_evidence'):
         gmean, gvar, _ = uqnet.predict_glm(xgrid, msc=1)
         print("  linearised (GLM) predictive in closed form beside the sampled one:")
         for xg, m, s, gm, gs in zip(xgrid[:, 0], ymean, ystd, gmean[:, 0], np.sqrt(gvar[:, 0])):
             print(f"  x={xg:+.3f}  sampled mean={m:+.4f} std={s:.4f}   glm mean={gm:+.4f} std={gs:.4f}")
     rmse = float(np.sqrt(np.mean((uqnet.predict_ens(xtst, nens=y.shape[0]).mean(axis=0) - ytst) ** 2))) \
-        if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
+        if meth in ('vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'swag') else float(np.sqrt(np.mean((predict(xtst).mean(axis=0) - ytst) ** 2)))
     print(f"  test RMSE of the predictive mean: {rmse:.4f}")
     if meth in ('amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts'):
         dg = dict(uqnet.diagnostics, pred=uqnet.diagnose(xgrid, nburn=1000 // k, nens=100 // k * 2)['pred'])

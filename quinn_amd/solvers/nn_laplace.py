@@ -34,7 +34,7 @@ import warnings
 import numpy as np
 import torch
 
-from .. import _lib, scoring
+from .. import _lib, evidence, scoring
 from ..ops import BatchedMLP, check_kron_args, kron_sample
 from .nn_rms import NN_RMS
 
@@ -64,10 +64,16 @@ GGN_TYPES = ('ggn', 'ggn_diag')
 
 def glm_mixture(f, S, noise_var=0.0):
     """Moments of the equal-weight mixture of M Gaussians N(f[b, n], S[b, n]) per query point (law of total variance):
-    mean = avg_b f_b,  cov = avg_b (S_b + f_b f_b^T) - mean mean^T, plus noise_var on the diagonal.
+    mean = avg_b f_b,  cov = avg_b (S_b + f_b f_b^T) - mean mean^T, plus noise_var on the diagonal.  noise_var `[M]` gives
+    every member its own level: member b predicts N(f_b, S_b + noise_var_b I), which adds avg_b noise_var_b.
     f (M, N, o), S (M, N, o, o) -> (mean (N, o), cov (N, o, o)), numpy float64."""
     f = np.asarray(f, dtype=np.float64)
     S = np.asarray(S, dtype=np.float64)
+    if np.ndim(noise_var) != 0:
+        noise_var = np.asarray(noise_var, dtype=np.float64)
+        if noise_var.shape != (f.shape[0],):
+            raise ValueError(f"noise_var of shape {noise_var.shape}: one level, or one per member ({f.shape[0]})")
+        noise_var = noise_var.mean()
     mean = f.mean(axis=0)
     second = (S + f[..., :, None] * f[..., None, :]).mean(axis=0)
     cov = second - mean[:, :, None] * mean[:, None, :]
@@ -91,6 +97,14 @@ class NN_Laplace(NN_RMS):
         self.kron = []              # 'kron': per member a dict of per-layer device tensors (see `_store_kron`)
         self._kron_packed = []      # 'kron': per member (UA [lenA], US [lenS], Dinv [p], Dih [p]) as the kernels take them
         self._kron_stack = None     # the members' packed tensors and means stacked (built on first use)
+        self._G_dev = []            # 'ggn' / 'ggn_diag': the members' Gauss-Newton curvature G as the kernel returned it (device)
+        self._ev_fit = None         # (xtrn, ytrn) of `fit`, and per `la_calc` member its (xtrn, ytrn): what the evidence's SSE needs
+        self._ev_calc = []
+        self._ev_cache = None       # (members, c [B, p], W [B, p], sse [B], n) of the evidence, built on its first call
+        self._ev_logZ = None        # the members' log evidence at the scales in use (None: not computed yet)
+        self.datanoise_ = None      # `tune_hyper(apply=True)`: the members' own noise levels [nens] ...
+        self.prior_prec_ = None     # ... and prior precisions [nens, G] of the groups `prior_groups_`
+        self.prior_groups_ = None
 
     def _kind(self):
         if self.la_type not in ('full', 'diag', 'kron') + GGN_TYPES:
@@ -130,6 +144,7 @@ class NN_Laplace(NN_RMS):
         self.cov_mats.append(cov_np)
         self._factors.append(None)
         self._cov_dev.append(cov)
+        self._G_dev.append(G)
         return H_np
 
     def _store_kron(self, W, A, S, lay, nb):
@@ -210,8 +225,8 @@ class NN_Laplace(NN_RMS):
             check_kron_args(self.arch, self._dtype)
         super().fit(xtrn, ytrn, **kwargs)
         W = np.asarray(self.fit_results['final_w'], dtype=np.float64)
-        op = BatchedMLP(self.arch, np.asarray(xtrn, dtype=np.float64), np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1),
-                        device=self._device)
+        self._ev_fit = (np.asarray(xtrn, dtype=np.float64), np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1))
+        op = BatchedMLP(self.arch, self._ev_fit[0], self._ev_fit[1], device=self._device)
         if kind == 'kron':
             A, S, lay = op.kron_factors(W, row_idx=self.rows)
             self._store_kron(W, A, S, lay, np.asarray(self.rows).reshape(len(W), -1).shape[1])
@@ -234,6 +249,7 @@ class NN_Laplace(NN_RMS):
         xtrn = np.asarray(xtrn, dtype=np.float64).reshape(len(xtrn), -1)
         ytrn = np.asarray(ytrn, dtype=np.float64).reshape(len(xtrn), -1)
         ntrn = len(xtrn)
+        self._ev_calc.append((xtrn, ytrn))
         op = BatchedMLP(self.arch, xtrn, ytrn, device=self._device)
         if kind == 'kron':                      # factor sums add over the batches; the single 1 / Nb uses the total row count
             check_kron_args(self.arch, self._dtype)
@@ -338,7 +354,8 @@ class NN_Laplace(NN_RMS):
         member b predicts N(f_b(x_n), J_n Sigma_b J_n^T) and the members are mixed with equal weights (`glm_mixture`).
         Returns (ymean (N,o), yvar (N,o) | None, ycov (N,o,o) | None); msc = 0 / 1 / 2 selects how much is returned.
         `ycov` is the covariance ACROSS THE OUTPUTS at each query point -- not `predict_mom_sample`'s (N,N,o), which is the
-        covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal.
+        covariance across the query points per output.  noise=True adds datanoise^2 to the (co)variance diagonal (after
+        `tune_hyper(apply=True)`: every member's own tuned level).
         One `qn_mlp_glm_predict` call over all members ('kron': `qn_mlp_kron_glm_predict`, no p x p array); no weight draws and
         no SVD.  Works for every la_type; with 'full' the covariance may not be positive semi-definite, and negative variances
         are reported (warned about, not clipped)."""
@@ -347,7 +364,7 @@ class NN_Laplace(NN_RMS):
         if not self.means:
             raise RuntimeError("predict_glm needs a fitted solver (fit or la_calc)")
         f, S = self._glm_members(x)
-        mean, cov = glm_mixture(f.cpu().numpy(), S.cpu().numpy(), self.datanoise ** 2 if noise else 0.0)
+        mean, cov = glm_mixture(f.cpu().numpy(), S.cpu().numpy(), self._member_noise_var() if noise else 0.0)
         var = np.stack([cov[:, k, k] for k in range(cov.shape[1])], axis=1)
         if np.any(var < 0):
             warnings.warn("predict_glm: negative predictive variance (the posterior covariance is not positive "
@@ -357,16 +374,164 @@ class NN_Laplace(NN_RMS):
     def score_glm(self, x, y, noise=None, crps=True, levels=scoring.DEFAULT_LEVELS, loo=False):
         """Score the closed-form linearised predictive against the targets y `(N, o)` at x: the dict of `QUiNNBase.score`, with
         member b predicting N(f_b(x_n)_k, noise^2 + (J_n Sigma_b J_n^T)_kk) per entry -- the members' means and the diagonal of
-        their predictive covariances go to `qn_pred_score` as F and V.  No weight draws; `noise` defaults to `datanoise`.
+        their predictive covariances go to `qn_pred_score` as F and V.  No weight draws; `noise` defaults to `datanoise`
+        (after `tune_hyper(apply=True)`: to every member's own tuned level, which then goes into V).
         With la_type 'full' a negative predictive variance makes that entry's scores NaN.  loo=True adds the PSIS-LOO keys, as
         in `QUiNNBase.score`."""
-        sigma = self._score_noise(noise)
+        own = noise is None and self.datanoise_ is not None
+        sigma = 0.0 if own else self._score_noise(noise)
         y = np.asarray(y, dtype=np.float64).reshape(len(x), -1)
         f, S = self._glm_members(x)
         M = f.shape[0]
         V = torch.diagonal(S, dim1=-2, dim2=-1).contiguous()
+        if own:
+            V = V + torch.as_tensor(self.datanoise_ ** 2, device=V.device)[:, None, None]
         what = scoring.WHAT_ALL if crps else scoring.WHAT_ALL & ~_lib.SCORE_CRPS
         yt = torch.as_tensor(y.reshape(-1), device=f.device)
         F, V = f.contiguous().reshape(M, -1), V.reshape(M, -1)
         loo_rows = scoring.psis_rows(F, yt, sigma, V).cpu().numpy() if loo else None
         return scoring.summarise_all(scoring.score_rows(F, yt, sigma, V, what).cpu().numpy(), loo_rows, y, M, levels)
+
+    # -- evidence ---------------------------------------------------------------------------------
+    def _member_noise_var(self):
+        """datanoise^2, or the members' own `[M]` after `tune_hyper(apply=True)`."""
+        return self.datanoise ** 2 if self.datanoise_ is None else self.datanoise_ ** 2
+
+    def _evidence_inputs(self):
+        """(c [B, p], W [B, p], sse [B], n) of all members, float64 device tensors: the curvature spectrum in units of G (see
+        `quinn_amd.evidence`), the MAP weights in flat order and the SSE on the member's own rows -- ONE `BatchedMLP.sse` call
+        for the members of `fit`, made on the first call and cached, like the spectrum."""
+        evidence.check_groups(self._kind(), 'all')
+        B = len(self.means)
+        if B == 0:
+            raise RuntimeError("the evidence needs a fitted solver (fit or la_calc)")
+        if self._ev_cache is not None and self._ev_cache[0] == B:
+            return self._ev_cache[1:]
+        W = np.asarray(self.means)
+        if self._ev_fit is not None and B == self.nens:
+            op = BatchedMLP(self.arch, self._ev_fit[0], self._ev_fit[1], device=self._device)
+            sse = op.sse(W, row_idx=self.rows)
+            n = np.asarray(self.rows).reshape(B, -1).shape[1] * self._ev_fit[1].shape[1]
+            dev = op.device
+        elif len(self._ev_calc) == B:
+            ns = {y.size for _, y in self._ev_calc}
+            if len(ns) != 1:
+                raise ValueError(f"the members of la_calc saw {sorted(ns)} entries of y: one evidence call needs the same n")
+            ops = [BatchedMLP(self.arch, x, y, device=self._device) for x, y in self._ev_calc]
+            sse = torch.cat([op.sse(W[j][None]) for j, op in enumerate(ops)])
+            n, dev = ns.pop(), ops[0].device
+        else:
+            raise RuntimeError("the evidence needs the data of every member: members of `fit` and of `la_calc` are not mixed")
+        if self.la_type == 'kron':
+            c = torch.stack([evidence.kron_spectrum(k["lamS"], k["lamA"], k["nb"]) for k in self.kron])
+        elif self.la_type == 'ggn_diag':
+            c = torch.stack(self._G_dev)
+        else:
+            c = torch.linalg.eigvalsh(torch.stack(self._G_dev)).clamp_min(0.0)
+        self._ev_cache = (B, c.contiguous(), torch.as_tensor(W, device=dev).contiguous(), sse.contiguous(), int(n))
+        return self._ev_cache[1:]
+
+    def _fit_scales(self):
+        """(s2, tau) of the fit as float64 numpy scalars."""
+        return np.float64(self.datanoise) ** 2, 1.0 / np.float64(self.priorsigma) ** 2
+
+    def log_marginal_likelihood(self, datanoise=None, priorsigma=None, groups='all', full=False):
+        """The Laplace approximation of every member's log marginal likelihood at its MAP weights (`quinn_amd.evidence`,
+        `qn_la_evidence`): `[nens]` at the fit's own `datanoise` and `priorsigma`.  Over a grid -- datanoise `[Hc]` and / or
+        priorsigma `[Hc]` or `[Hc, G]` (one scale per group of `groups`: 'all', 'layer', or 'tensor' for 'ggn_diag'), broadcast
+        against each other; what is not given stays the fit's -- the result is `[nens, Hc]`.  full=True returns the dict of all
+        rows: `logZ`, `loglik`, `logdet`, `gamma` (the effective number of parameters) and `gamma_g`, `S_g` `[..., G]`.
+        la_type 'ggn', 'ggn_diag' and 'kron' ('ggn': groups='all' only; 'kron': not 'tensor').  `cov_scale` plays no part."""
+        evidence.check_groups(self._kind(), groups)
+        c, W, sse, n = self._evidence_inputs()
+        bounds, _ = evidence.group_bounds(self.arch, groups)
+        B, G = c.shape[0], len(bounds) - 1
+        grid = np.ndim(datanoise) > 0 or np.ndim(priorsigma) > 0
+        s2_fit, tau_fit = self._fit_scales()
+        s2 = s2_fit if datanoise is None else np.asarray(datanoise, dtype=np.float64) ** 2
+        tau = tau_fit if priorsigma is None else 1.0 / np.asarray(priorsigma, dtype=np.float64) ** 2
+        if np.ndim(s2) > 1 or np.ndim(tau) > 2 or (np.ndim(tau) == 2 and tau.shape[1] != G):
+            raise ValueError(f"datanoise is a scalar or [Hc], priorsigma a scalar, [Hc] or [Hc, {G}]")
+        tau = np.asarray(tau)[..., None] if np.ndim(tau) < 2 else tau
+        try:
+            Hc = np.broadcast_shapes(np.shape(s2), tau.shape[:-1], (1,))[0]
+        except ValueError:
+            raise ValueError("datanoise and priorsigma do not broadcast against each other") from None
+        s2 = np.ascontiguousarray(np.broadcast_to(s2, (B, Hc)))
+        tau = np.ascontiguousarray(np.broadcast_to(tau, (B, Hc, G)))
+        out = evidence.log_evidence_dev(c, W, sse, n, bounds, torch.as_tensor(s2, device=c.device),
+                                        torch.as_tensor(tau, device=c.device)).cpu().numpy()
+        if not grid:
+            out = out[:, 0]
+            if datanoise is None and priorsigma is None and self._ev_logZ is None:
+                self._ev_logZ = out[:, 0].copy()
+        if not full:
+            return out[..., 0]
+        no = len(evidence.ROWS)
+        res = {name: out[..., i] for i, name in enumerate(evidence.ROWS)}
+        res.update(gamma_g=out[..., no:no + G], S_g=out[..., no + G:])
+        return res
+
+    def tune_hyper(self, groups='layer', tol=evidence.DEFAULT_TOL, max_iter=evidence.DEFAULT_MAX_ITER, tune_noise=True,
+                   tune_prior=True, apply=True):
+        """Empirical Bayes, post hoc: every member's noise level and per-group prior precisions by maximising its Laplace evidence
+        at its MAP weights (MacKay's fixed point, `quinn_amd.evidence.tune`), one `qn_la_tune` launch for all members, from the
+        fit's scales.  Returns a dict: `datanoise` `[nens]`, `prior_prec` `[nens, G]`, `prior_groups` (the groups' names),
+        `logZ`, `logZ_start`, `gamma` `[nens, G]`, `iters`, `converged`, `clamped` (the OR of the `evidence.CLAMP_` bits), `resid`.
+        A member that did not converge within max_iter returns the best iterate seen, so logZ >= logZ_start always.
+        apply=True rebuilds every member's posterior at its own tuned scales ('kron', 'ggn_diag': the variances come from the
+        same launch; 'ggn': one device Cholesky per member); `predict_ens`, `predict_glm` and `score_glm` then use them, and
+        their noise default becomes each member's own level.  The tuned values are kept in `datanoise_` / `prior_prec_`;
+        `datanoise` / `priorsigma` stay the fit's.  The MAP weights are not refitted."""
+        evidence.check_groups(self._kind(), groups)
+        c, W, sse, n = self._evidence_inputs()
+        bounds, names = evidence.group_bounds(self.arch, groups)
+        B, G = c.shape[0], len(bounds) - 1
+        s2_fit, tau_fit = self._fit_scales()
+        s2_0 = torch.full((B,), float(s2_fit), dtype=torch.float64, device=c.device)
+        tau_0 = torch.full((B, G), float(tau_fit), dtype=torch.float64, device=c.device)
+        want = bool(apply) and self.la_type in ('kron', 'ggn_diag')
+        dev = evidence.tune_dev(c, W, sse, n, bounds, s2_0, tau_0, tol=tol, max_iter=max_iter, tune_noise=tune_noise,
+                                tune_prior=tune_prior, cov_scale=self.cov_scale, want_dinv=want)
+        s2, tau, rows, status = (dev[k].cpu().numpy() for k in ("s2", "tau", "rows", "status"))
+        no = len(evidence.ROWS)
+        res = dict(datanoise=np.sqrt(s2), prior_prec=tau, prior_groups=list(names), logZ=rows[:, 0], logZ_start=status[:, 4],
+                   gamma=rows[:, no:no + G], iters=status[:, 0].astype(np.int64), converged=status[:, 2].astype(bool),
+                   clamped=status[:, 5].astype(np.int64), resid=status[:, 3])
+        if not apply:
+            return res
+        if np.any(np.isnan(rows[:, 0])):
+            raise np.linalg.LinAlgError("tune_hyper: the evidence of a member is NaN (a non-finite weight, curvature or SSE); "
+                                        "nothing was applied")
+        if self.la_type == 'kron':
+            for j in range(B):
+                UA, US = self._kron_packed[j][:2]
+                self._kron_packed[j] = (UA, US, dev["Dinv"][j], dev["Dih"][j])
+                lay = self.kron[j]["layout"]
+                self.kron[j]["Dinv"] = [lay.K(dev["Dinv"][j], i) for i in range(len(lay.e))]
+            self._kron_stack = None
+        elif self.la_type == 'ggn_diag':
+            for j in range(B):
+                self._cov_dev[j] = dev["Dinv"][j]
+                self.cov_mats[j] = np.diag(dev["Dinv"][j].cpu().numpy())
+                self._factors[j] = None
+        else:
+            for j in range(B):
+                H = self._G_dev[j] / dev["s2"][j]
+                H.diagonal().add_(dev["tau"][j, 0])
+                chol, info = torch.linalg.cholesky_ex(H * self.cov_scale)
+                if int(info) != 0:
+                    raise np.linalg.LinAlgError(f"Cholesky factorisation of the tuned Gauss-Newton Hessian of member {j} failed")
+                cov = torch.cholesky_inverse(chol)
+                cov = 0.5 * (cov + cov.mT)
+                self._cov_dev[j], self.cov_mats[j], self._factors[j] = cov, cov.cpu().numpy(), None
+        self.datanoise_, self.prior_prec_, self.prior_groups_ = res["datanoise"].copy(), tau.copy(), list(names)
+        self._ev_logZ = res["logZ"].copy()
+        return res
+
+    def evidence_weights(self):
+        """`[nens]`: the softmax of the members' log evidence (numpy) at the scales in use -- the tuned ones after
+        `tune_hyper(apply=True)`, else the fit's -- for `score(..., member_weights=)` of one draw per member in member order."""
+        if self._ev_logZ is None:
+            self.log_marginal_likelihood()
+        return evidence.softmax_weights(self._ev_logZ)
