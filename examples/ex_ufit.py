@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The reference's `examples/ex_ufit.py` call pattern on the MI355X path.
 
-    python examples/ex_ufit.py {amcmc|hmc|stack|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|laplace_evidence|swag} [--quick] [--mlp]
+    python examples/ex_ufit.py {amcmc|hmc|stack|quantiles|pt|sghmc|prior|hyper|noise|ess|nuts|vi|ens|rms|laplace|laplace_ggn|laplace_kron|laplace_evidence|swag} [--quick] [--mlp]
 
 Same data generation, same network (`RNet(3, 3, wp_function=Poly(0), ...)`, examples/ex_ufit.py:72-77
 there; `--mlp` switches to the commented-out MLP alternative), same solver calls and keyword
@@ -17,6 +17,9 @@ log evidence before and after, the tuned scales and the held-out nlpd of `score_
 step size, every 10th state stored; MLP network),
 `stack` is the device HMC (`engine='device'`; MLP network) whose 8 chains are stacked (`NN_MCMC.stack`: PSIS-LOO density per chain,
 EM for the weights on the device) and scored on the test rows with equal and with stacking weights,
+`quantiles` is the same stacked device HMC, printing the 90 % credible band of the predictive on the test rows
+(`predict_interval`: quantiles of the Gaussian mixture with the data noise, found on the device) -- its width, coverage and
+interval score (`scoring.interval_summary`) with equal and with stacking weights, beside the epistemic band without the noise,
 `pt` is the device HMC with replica exchange (`engine='device'`, 8 ladders of 4 rungs; predictions and diagnostics from the cold
 chains; MLP network),
 `prior` is the device HMC with the Gaussian weight prior `priorsigma=1.0` (`engine='device'`; MLP network), printed beside the same
@@ -54,7 +57,7 @@ def Sine(xx, datanoise=0.0):
 
 def main(meth, quick=False, mlp=False):
     torch.set_default_dtype(torch.double)
-    all_uq_options = ['amcmc', 'hmc', 'stack', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'swag']
+    all_uq_options = ['amcmc', 'hmc', 'stack', 'quantiles', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
     nall, trn_factor, ntst, ndim, datanoise = 15, 0.9, 13, 1, 0.02
     if meth == 'laplace_evidence':       # the evidence's fixed point needs more entries of y than effective parameters
@@ -65,7 +68,7 @@ def main(meth, quick=False, mlp=False):
     np.random.seed(100)
     xtst = scale01ToDom(np.random.rand(ntst, ndim), domain)
     ytst = Sine(xtst, datanoise=datanoise)
-    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'sghmc', 'stack', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
+    if mlp or meth in ('laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'sghmc', 'stack', 'quantiles', 'pt', 'prior', 'hyper', 'noise', 'ess', 'nuts'):    # the Laplace curvature kernels take MLPs (RNet is not covered); sghmc runs the MLP too
         nnet = MLP(ndim, 1, (11, 11, 11), biasorno=True, activ='tanh')
     else:
         nnet = RNet(3, 3, wp_function=Poly(0), indim=ndim, outdim=1, layer_pre=True, layer_post=True,
@@ -102,6 +105,22 @@ def main(meth, quick=False, mlp=False):
                   f"90 % coverage {sc['coverage'][0.9]:.2f}")
         sm, sv = uqnet.predict_mom_stacked(xtst)
         print(f"  stacked predictive on the test rows: mean |mean - y| {np.mean(np.abs(sm - ytst)):.4f}, mean std {np.mean(np.sqrt(sv)):.4f}")
+    elif meth == 'quantiles':
+        from quinn_amd import scoring
+        uqnet = NN_MCMC(nnet, verbose=not quick)
+        uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',
+                  sampler_params={'L': 3, 'epsilon': 0.0025}, seeds=range(8), diagnostics=True)
+        ens = dict(nsam=100 // k * 8, nburn=1000 // k)
+        predict = lambda x: uqnet.predict_ens(x, nens=ens['nsam'], nburn=ens['nburn'], chain='all')
+        st = uqnet.stack(xtrn, ytrn, loo=True, **ens)
+        print("  stacking weights of the chains:", np.round(st['weights'], 4))
+        for label, wm in (('equal weights', None), ('stacked', st['member_weights'])):
+            lo, med, hi = uqnet.predict_interval(xtst, level=0.9, chain='all', member_weights=wm, **ens)
+            band = scoring.interval_summary(lo, hi, ytst, 0.9)
+            print(f"  90 % band on the test rows, {label}: width {band['width']:.4f}  coverage {band['coverage']:.2f}  "
+                  f"interval score {band['interval_score']:.4f}  mean |median - y| {np.mean(np.abs(med - ytst)):.4f}")
+        lo, _, hi = uqnet.predict_interval(xtst, level=0.9, noise=0, chain='all', **ens)
+        print(f"  epistemic 90 % band (no data noise, order statistics of the members): width {np.mean(hi - lo):.4f}")
     elif meth == 'pt':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='hmc', engine='device',

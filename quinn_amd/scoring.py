@@ -9,7 +9,9 @@ O(M^2 K) evaluations.  With loo=True a second device call (`qn_psis_loo`, csrc/q
 importance-sampling leave-one-out scores: `elpd_loo`, the per-entry `khat` that says where it can be trusted, and the LOO-PIT
 (`psis.py` is their contract in numpy).  `group_lpd`, `stack_weights` and `member_weights=` are the stacking of groups of
 members -- chains that did not mix, deep-ensemble members -- on the device (`qn_group_lpd`, `qn_stack_weights`,
-`qn_pred_score_w`, csrc/qn_stack.hip; `stacking.py` is their contract, include/quinn_amd_stack.h their header).  Rank histograms and energy scores across outputs are out of scope.  The reference
+`qn_pred_score_w`, csrc/qn_stack.hip; `stacking.py` is their contract, include/quinn_amd_stack.h their header).  `quantile_rows`,
+`pred_quantiles` and `interval_summary` are the inverse of the PIT: the quantiles and credible bands of the same mixture
+(`qn_pred_quantile`, csrc/qn_quantile.hip; `predquant.py` is the contract, include/quinn_amd_quantile.h the header).  Rank histograms and energy scores across outputs are out of scope.  The reference
 has no counterpart; the per-entry definitions are in include/quinn_amd.h at `qn_pred_score` and in include/quinn_amd_psis.h at `qn_psis_loo`.
 """
 
@@ -219,6 +221,70 @@ def stack_weights(L, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, block=64):
     s = final.numpy()
     return {"w": wh, "obj": float(s[0]), "gap": float(s[1]), "iters": int(s[2]), "n_kept": int(s[3]), "n_nonfinite": int(s[4]),
             "n_dropped": int(s[5]), "obj_equal": float(s[6])}
+
+
+def quantile_rows(F, q, noise, V=None, wm=None, return_iters=False):
+    """`qn_pred_quantile` on device tensors: F `(M, K)` float64 / float32 contiguous, V the same or None, wm `(M,)` float64
+    member weights or None (1 / M), q the levels (host values) -> `[Q, K]` float64 device tensor of the quantiles of the
+    mixture sum_m wm_m N(f_mk, noise^2 + V_mk).  noise == 0 without V: the order-statistic quantiles of the members, levels
+    in [0, 1]; otherwise the roots of the mixture's distribution function, levels in (0, 1).  return_iters: also the `(K,)`
+    int32 device tensor of the largest number of evaluations an entry's levels took (0 in the order-statistic mode)."""
+    M, K = F.shape
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1))
+    Q = q.size
+    L = _lib.lib()
+    need = int(L.qn_pred_quantile_workspace_bytes(M, K, Q, int(float(noise) == 0.0 and V is None)))
+    if need == 0:
+        raise ValueError(L.qn_last_error().decode())
+    _check_fvy(F, V, None)
+    if wm is not None and (wm.shape != (M,) or wm.dtype != torch.float64 or wm.device != F.device):
+        raise ValueError(f"member_weights: a float64 tensor of {M} weights on F's device is needed")
+    out = torch.empty((Q, K), dtype=torch.float64, device=F.device)
+    iters = torch.empty(K, dtype=torch.int32, device=F.device) if return_iters else None
+    ws = torch.empty(need // 8, dtype=torch.float64, device=F.device)
+    qdt = _lib.QN_F32 if F.dtype == torch.float32 else _lib.QN_F64
+    with torch.cuda.device(F.device):
+        st = _lib.stream(F.device)
+        rc = L.qn_pred_quantile(F.data_ptr(), V.data_ptr() if V is not None else None, qdt,
+                                wm.data_ptr() if wm is not None else None, M, K, float(noise), q.ctypes.data, Q, out.data_ptr(),
+                                iters.data_ptr() if iters is not None else None, ws.data_ptr(), need, st)
+    if rc == _lib.CONSTANTS["QN_EINVAL"]:
+        raise ValueError(L.qn_last_error().decode())
+    _lib.check(rc, "qn_pred_quantile")
+    return (out, iters) if return_iters else out
+
+
+def pred_quantiles(F, q, noise, V=None, member_weights=None, device=None):
+    """The quantiles at the levels q of the predictive of the ensemble F `(M, N, o)` or `(M, K)` (device tensor or numpy;
+    float32 is read as it is, all arithmetic is float64): member m predicts N(F[m], noise^2 + V[m]), mixed with the weights
+    member_weights `(M,)` (>= 0, sum 1; None: equal).  Returns numpy `(Q,) + F.shape[1:]`.  noise = 0 without V gives the
+    order-statistic quantiles of the members (np.quantile's default method with equal weights).  Only the `Q x K` result
+    leaves the device."""
+    if isinstance(F, torch.Tensor) and F.is_cuda:
+        dev = F.device
+    else:
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    shape = tuple(F.shape[1:])
+    K = int(np.prod(shape))
+    Ft = _ens_tensor(F, K, dev, "F")
+    Vt = None if V is None else _ens_tensor(V, K, dev, "V").to(Ft.dtype)
+    wm = None if member_weights is None else torch.as_tensor(np.asarray(member_weights, dtype=np.float64).reshape(-1), device=dev)
+    rows = quantile_rows(Ft, q, noise, Vt, wm).cpu().numpy()
+    return rows.reshape((rows.shape[0],) + shape)
+
+
+def interval_summary(qlo, qhi, y, level):
+    """The width, coverage and interval score of the central `level` band [qlo, qhi] against the targets y (numpy, any common
+    shape): `width` = mean(qhi - qlo), `coverage` = the share of y inside the closed band, `interval_score` = the mean
+    Winkler score, width + (2 / (1 - level)) (distance of y outside the band) (Gneiting & Raftery, JASA 102, 2007), and `n`."""
+    qlo, qhi, y = (np.asarray(a, dtype=np.float64) for a in (qlo, qhi, y))
+    if not (qlo.shape == qhi.shape == y.shape) or y.size < 1 or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"qlo {qlo.shape}, qhi {qhi.shape} and y {y.shape} must share a shape, and 0 < level < 1")
+    width = qhi - qlo
+    outside = np.maximum(qlo - y, 0.0) + np.maximum(y - qhi, 0.0)
+    return {"n": int(y.size), "level": float(level), "width": float(width.mean()),
+            "coverage": float(np.mean((y >= qlo) & (y <= qhi))),
+            "interval_score": float(np.mean(width + (2.0 / (1.0 - float(level))) * outside))}
 
 
 def summarise_all(rows, loo_rows, y, M, levels=DEFAULT_LEVELS):

@@ -392,6 +392,27 @@ class NN_Laplace(NN_RMS):
         loo_rows = scoring.psis_rows(F, yt, sigma, V).cpu().numpy() if loo else None
         return scoring.summarise_all(scoring.score_rows(F, yt, sigma, V, what).cpu().numpy(), loo_rows, y, M, levels)
 
+    def predict_glm_quantiles(self, x, q=(0.05, 0.5, 0.95), msc=1, noise=False):
+        """`(Q, N, o)`: the quantiles at the levels q (0 < q < 1) of the closed-form linearised predictive of `predict_glm` --
+        the equal-weight mixture of the members' Gaussians N(f_b(x_n)_k, (J_n Sigma_b J_n^T)_kk) per entry, with noise=True
+        plus datanoise^2 (every member's own tuned level after `tune_hyper(apply=True)`).  The members' means and the diagonal
+        of their predictive covariances go to `qn_pred_quantile` as F and V; no weight draws.  msc = 0 keeps the members'
+        means only: the order-statistic quantiles of the f_b (levels in [0, 1]).  With la_type 'full' a variance that is not
+        positive makes that entry NaN."""
+        if msc not in (0, 1, 2):
+            raise ValueError(f"msc={msc}, but needs to be 0, 1 or 2")
+        f, S = self._glm_members(x)
+        M, N, o = f.shape
+        F = f.contiguous().reshape(M, -1)
+        V = torch.diagonal(S, dim1=-2, dim2=-1).contiguous() if msc >= 1 else None
+        if noise:
+            nv = np.array(np.broadcast_to(np.asarray(self._member_noise_var(), dtype=np.float64), (M,)))
+            nv = torch.as_tensor(nv, device=f.device)[:, None, None]
+            V = nv.expand(M, N, o) if V is None else V + nv
+        if V is not None:
+            V = V.reshape(M, -1).contiguous()
+        return scoring.quantile_rows(F, q, 0.0, V).cpu().numpy().reshape(-1, N, o)
+
     # -- evidence ---------------------------------------------------------------------------------
     def _member_noise_var(self):
         """datanoise^2, or the members' own `[M]` after `tune_hyper(apply=True)`."""

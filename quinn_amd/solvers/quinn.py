@@ -260,6 +260,48 @@ class QUiNNBase():
                 loo_rows[:, lo * o:hi * o] = scoring.psis_rows(F, yt, sigma, V).cpu().numpy()
         return scoring.summarise_all(rows, loo_rows, y, M, levels)
 
+    # -- quantiles and credible bands of the predictive (qn_pred_quantile) ------------------------------------
+    def predict_quantiles(self, x, q=(0.05, 0.5, 0.95), noise=None, nsam=1000, member_weights=None, max_bytes=256 << 20,
+                          **ens_args):
+        """`(Q, N, o)`: the quantiles at the levels q of the predictive that `score` judges -- member m of the solver's
+        `nsam`-member ensemble predicts N(f_m(x), noise^2), mixed with equal weights or with member_weights `(M,)`
+        (`stack(...)['member_weights']`, with the nsam and ens_args `stack` was called with; the members then come in the
+        order of `_ens_weights_ordered`).  `noise` defaults to the data noise of the last fit (a solver that sampled the noise
+        level: every member at its own level); noise=0 or False gives the epistemic order-statistic quantiles of the members,
+        np.quantile's default method, where the levels may be 0 and 1.  The weights are drawn ONCE, then x is walked in the
+        row chunks of `score`: one batched forward and one `qn_pred_quantile` per chunk, and only `Q x rows x o` doubles are
+        downloaded.  An entry's quantiles do not depend on the chunking."""
+        epistemic = noise is not None and float(noise) == 0.0
+        member = None if epistemic else self._score_member_noise(noise, nsam, **ens_args)
+        sigma = 0.0 if (epistemic or member is not None) else self._score_noise(noise)
+        x = np.asarray(x, dtype=np.float64).reshape(len(x), -1)
+        q = np.asarray(q, dtype=np.float64).reshape(-1)
+        W = self._ens_weights(nsam, **ens_args) if member_weights is None else self._ens_weights_ordered(nsam, **ens_args)
+        M, N = len(W), len(x)
+        wm = None
+        if member_weights is not None:
+            wm = np.asarray(member_weights, dtype=np.float64).reshape(-1)
+            if wm.shape != (M,):
+                raise ValueError(f"member_weights holds {wm.size} weights for an ensemble of {M} members")
+        out = None
+        for lo, hi, F, _, V in self._score_chunks(W, x, None, member, max_bytes):
+            if wm is not None:
+                wm = torch.as_tensor(wm, device=F.device)
+            rows = scoring.quantile_rows(F, q, sigma, V, wm).cpu().numpy().reshape(q.size, hi - lo, -1)
+            if out is None:
+                out = np.empty((q.size, N, rows.shape[2]))
+            out[:, lo:hi] = rows
+        return out
+
+    def predict_interval(self, x, level=0.9, **kwargs):
+        """(lo, median, hi), each `(N, o)`: the central credible band of the predictive at `level` and its median -- the
+        quantiles (1 - level) / 2, 0.5 and (1 + level) / 2 of `predict_quantiles` (kwargs as there)."""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError(f"level = {level}; 0 < level < 1 is needed")
+        lo, mid, hi = self.predict_quantiles(x, q=(0.5 * (1.0 - level), 0.5, 0.5 * (1.0 + level)), **kwargs)
+        return lo, mid, hi
+
     # -- figures (presentation only; same signatures and file names as quinn.py:106-260) ---------------
     @staticmethod
     def _center_and_spread(yens, quantiles):
