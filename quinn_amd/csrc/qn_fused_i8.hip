@@ -18,6 +18,8 @@
 //   L >= LMIN = 4 are kept (26 of 36 products; the dropped ones are < 2^-51 of the row scale), recombined exactly in
 //   pairs (int32) and then in float64.  Error of a pre-activation: ~1e-14 relative to |W_j| (quantisation of a and w to
 //   2^-47), against ~2e-16 for the f64 MFMA chain -- both far inside the 1e-11 parity tolerance (tests).
+//   The digit arithmetic itself is pinned by tests/test_gpu_i8_slice_pin.py to the exact integer model of
+//   tests/test_i8_slice_ref_cpu.py: relu / identity bit for bit (counted roundings), tanh within a derived ~5e-16.
 //
 // Layout.  Z^T[feature x row] = W A^T per 16-row group: A operand = weight digits from LDS (lane: row = lane & 15,
 // 16 bytes = k-slots of lane group lane >> 4), B operand = activation digits (lane: column = data row = lane & 15, same
