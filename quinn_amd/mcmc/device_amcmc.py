@@ -65,10 +65,11 @@ def _toc(dev, t0, what, *args):
 
 
 class DeviceAMCMC(DeviceEngine):
-    def __init__(self, op, sigma, gamma=0.1, t0=100, tadapt=1000, cov_ini=None, seed=0,
-                 use_graph=False, max_history_bytes=64 << 30, chain0=0, fuse_propose=True, groups=None, max_rows=4096,
-                 overlap_hist=True, hist_scale0=256.0, pause_gc=True, priorsigma=None):
-        if op.dtype != "float64":
+    _kind = 'amcmc'
+
+    @classmethod
+    def check_params(cls, arch, dtype, nmcmc, priorsigma, hist_scale0=256.0, **rest):
+        if dtype != "float64":
             raise NotImplementedError("the device AMCMC engine runs the float64 operator")
         try:
             hs0_ok = bool(np.isfinite(hist_scale0)) and hist_scale0 > 0
@@ -76,6 +77,12 @@ class DeviceAMCMC(DeviceEngine):
             hs0_ok = False
         if not hs0_ok:                                      # (0, a negative number, NaN or inf: a NaN scale of the history rows)
             raise ValueError("hist_scale0 must be a finite number > 0, got %r" % (hist_scale0,))
+        return super().check_params(arch, dtype, nmcmc, priorsigma, **rest)
+
+    def __init__(self, op, sigma, gamma=0.1, t0=100, tadapt=1000, cov_ini=None, seed=0,
+                 use_graph=False, max_history_bytes=64 << 30, chain0=0, fuse_propose=True, groups=None, max_rows=4096,
+                 overlap_hist=True, hist_scale0=256.0, pause_gc=True, priorsigma=None):
+        self.check_params(None, op.dtype, None, priorsigma, hist_scale0=hist_scale0)      # (no rule reads the architecture)
         # groups > 1: a group's accept / propose kernel (a chain of memory round trips that leaves the GPU idle: 8.7 of a step's
         # 84 us at cfg2) overlaps the other group's forward kernel.  None: 2 groups from 32 chains on (measured at cfg2: 11.9 ->
         # 12.4 k steps/s before the first adaptation; 4 groups are bound by the enqueuing thread) when the fused kernels run the
@@ -188,7 +195,8 @@ class DeviceAMCMC(DeviceEngine):
                            overlap_hist=self.overlap_hist, hist_scale0=self.hist_scale0, pause_gc=False,
                            priorsigma=self.priorsigma)
 
-    def _merge_groups(self, out, res, engs):
+    def _merge_groups(self, out, res, engs, nmcmc):
+        super()._merge_groups(out, res, engs, nmcmc)
         self.last_state, self.last_states = None, [e.last_state for e in engs]      # (diagnostics: per group)
 
     @staticmethod

@@ -40,30 +40,34 @@ class DeviceESS(DeviceEngine):
     get there -- watch 'ntrunc' and raise it if truncated steps are not rare), block (iterations enqueued between two looks at the
     chains' step counters), plus the engine's seed / chain0 / groups."""
 
-    def __init__(self, op, sigma, priorsigma=None, seed=0, chain0=0, max_shrink=32, block=32, groups=None, use_graph=False,
-                 ladder=None):
+    _kind = 'ess'
+
+    @classmethod
+    def check_params(cls, arch, dtype, nmcmc, priorsigma, max_shrink=32, block=32, use_graph=False, ladder=None, **rest):
+        cfg = super().check_params(arch, dtype, nmcmc, priorsigma, **rest)
         if use_graph:
             raise ValueError("DeviceESS with use_graph=True: the number of iterations of a run is data dependent, there is no "
                              "fixed launch sequence to capture; run with use_graph=False")
         if ladder is not None:
             raise ValueError("DeviceESS with ladder: elliptical slice sampling is not tempered (the ellipse is the prior's); "
                              "replica exchange is for sampler='hmc' / 'mala'")
-        ps, self.max_shrink, self.block = check_ess_args(priorsigma, max_shrink, block)
-        super().__init__(op, sigma, seed, chain0, False, groups, ps)
-        self.last_iters = None                 # (diagnostics: iterations enqueued by the last run, and how many were needed)
+        if cfg['priorsigma'] is None:
+            raise ValueError("sampler='ess' needs priorsigma: elliptical slice sampling draws from the Gaussian weight prior "
+                             "N(0, priorsigma^2 I); pass fit(..., priorsigma=s) with s > 0")
+        cfg['ess'] = check_ess_args(priorsigma, max_shrink, block)
+        return cfg
 
-    def _ngroups(self, C):
-        if self.groups is None:
-            return 1
-        return min(self.groups, C)
+    def __init__(self, op, sigma, priorsigma=None, seed=0, chain0=0, max_shrink=32, block=32, groups=None, use_graph=False,
+                 ladder=None):
+        ps, self.max_shrink, self.block = self.check_params(op.arch, op.dtype, None, priorsigma, max_shrink=max_shrink, block=block,
+                                                            use_graph=use_graph, ladder=ladder)['ess']
+        super().__init__(op, sigma, seed, chain0, False, groups, ps)
 
     def _clone(self, op, chain0):
         return DeviceESS(op, self.sigma, self.priorsigma, self.seed, chain0, self.max_shrink, self.block, groups=1)
 
-    def _merge_groups(self, out, res, engs):
-        for k in ('nev', 'ntrunc', 'nevals'):
-            out[k] = torch.cat([r[k] for r in res])
-        self.last_iters = [e.last_iters for e in engs]
+    def _extra_keys(self, nmcmc):
+        return {'nev': ((nmcmc + 1,), np.int32), 'ntrunc': ((), np.int64), 'nevals': ((), np.int64)}
 
     def log_prior(self, W):
         """log N(w; 0, priorsigma^2 I) of every row of the device tensor W [C, p]: float64 [C]."""
@@ -110,31 +114,7 @@ class DeviceESS(DeviceEngine):
             cur.data_ptr(), sse0.data_ptr(), lp0.data_ptr(), self.sigma, self.priorsigma, C, self.chain0, p, self.seed,
             s['nu'].data_ptr(), s['prop'].data_ptr(), None if s['prop_op'] is None else s['prop_op'].data_ptr(), self.op.qdt,
             s['sq'].data_ptr(), s['es'].data_ptr(), s['ei'].data_ptr(), self._stream()), "qn_ess_begin")
-        # the smallest step counter after each block: reduced on the device, copied into pinned memory behind the block, and
-        # looked at one block late -- when the next block is already enqueued
-        tmin_dev = torch.empty(2, dtype=torch.int64, device=dev)
-        tmin_host = torch.zeros(2, dtype=torch.int64).pin_memory()
-        events = [torch.cuda.Event(), torch.cuda.Event()]
-        k = needed = 0
-        while True:
-            for _ in range(self.block):
-                self._iter(s, nmcmc)
-            torch.amin(s['ei'][s['par'], :, 0], dim=0, out=tmin_dev[k & 1])
-            tmin_host[k & 1].copy_(tmin_dev[k & 1], non_blocking=True)
-            events[k & 1].record(torch.cuda.current_stream(dev))
-            k += 1
-            yield
-            if k >= 2:
-                events[k & 1].synchronize()                        # block k - 2 (0-based): block k - 1 is already enqueued
-                tmin = int(tmin_host[k & 1])
-                if verbose:
-                    print('%d iterations enqueued, slowest chain at step %d / %d' % (k * self.block, tmin, nmcmc))
-                if tmin >= nmcmc:
-                    needed = (k - 1) * self.block
-                    break
-            if k * self.block >= nmcmc * self.max_shrink + 2 * self.block:      # (cannot happen: a step ends within max_shrink iterations)
-                raise _lib.QuinnAmdError("DeviceESS: the chains did not finish within nmcmc * max_shrink iterations")
-        self.last_iters = (k * self.block, needed)
+        yield from self._run_blocks(s, nmcmc, nmcmc * self.max_shrink + 2 * self.block, verbose)      # (a step ends within max_shrink iterations)
         par = s['par']
         ei = s['ei'][par]
         ntrunc = ei[:, 2].clone()

@@ -84,49 +84,56 @@ def _ptr(t):
 class DeviceHMC(DeviceEngine):
     _kind = 'hmc'
 
+    @classmethod
+    def check_params(cls, arch, dtype, nmcmc, priorsigma, nchains=None, chain0=0, hyperprior=None, noiseprior=None, L=3,
+                     use_graph=False, adapt=0, target_accept=None, ladder=None, beta_min=0.01, swap_every=1, **rest):
+        if int(L) < 1:
+            raise ValueError("HMC needs L >= 1 leapfrog steps")
+        cfg = super().check_params(arch, dtype, nmcmc, priorsigma)
+        # warm-up: `adapt` steps of dual averaging from `epsilon` towards `target_accept` (default 0.8; MALA 0.574)
+        cfg['target_accept'] = TARGET_ACCEPT[cls._kind] if target_accept is None else float(target_accept)
+        cfg['adapt'] = check_adapt_args(adapt, cfg['target_accept'])
+        # replica exchange: the inverse temperatures of one ladder (None: no tempering); all chains are whole ladders
+        cfg['ladder'] = None if ladder is None else check_temper_args(ladder, beta_min, swap_every, C=nchains, chain0=chain0,
+                                                                      use_graph=use_graph)
+        # hierarchical prior and noise prior: the settings (None: the scalar prior or none; the hand-set noise level)
+        cfg['hyperprior'], cfg['noiseprior'] = check_hyperprior(hyperprior), check_noiseprior(noiseprior)
+        for name, own, what in (('hyperprior', 'precisions', 'weight groups are defined'),
+                                ('noiseprior', 'noise level', 'the noise level is sampled')):
+            if cfg[name] is None:
+                continue
+            if cfg['ladder'] is not None:
+                raise ValueError(f"{name} does not run with a ladder (a tempered rung would need its own {own})")
+            if use_graph:
+                raise ValueError(f"{name} does not run with use_graph=True (the round counter changes from launch to launch)")
+            if type(arch).__name__ != 'MLPArch':
+                raise ValueError(f"{name}: {what} for plain MLPs, not for a residual network (RNet)")
+        if cfg['noiseprior'] is not None and dtype != 'float64':
+            raise ValueError("noiseprior needs a float64 operator (the fold's rescaling of a float32 gradient would round it "
+                             "a second time)")
+        cfg['seg'] = cfg['prior_groups'] = None
+        if cfg['hyperprior'] is not None:                  # the weight groups, known before any launch
+            seg, names = group_segments(arch, cfg['hyperprior']['groups'])
+            cfg['seg'] = check_segments(seg, arch.nparams)
+            initial_tau(cfg['hyperprior'], len(names), cfg['priorsigma'])      # (a tau0 of the wrong length is refused here)
+            cfg['prior_groups'] = [(n, int(lo), int(hi)) for n, lo, hi in zip(names, seg[:-1], seg[1:])]
+        return cfg
+
     def __init__(self, op, sigma, epsilon=0.05, L=3, seed=0, chain0=0, use_graph=False, groups=None, adapt=0,
                  target_accept=None, adapt_mass=True, ladder=None, beta_min=0.01, swap_every=1, priorsigma=None, hyperprior=None,
                  noiseprior=None):
         # groups: default 1.  Unlike the AMCMC engine's forward (two workgroups per CU, a lone one runs 1.8 x faster) the gradient
         # kernel puts ONE workgroup on a CU, so a group's launch cannot spread into the CUs the other group's small kernels leave
         # idle -- measured at cfg2: 1418 -> 1427 steps/s (HMC, L = 3), 4094 -> 4100 (MALA)
+        cfg = self.check_params(op.arch, op.dtype, None, priorsigma, chain0=chain0, hyperprior=hyperprior, noiseprior=noiseprior,
+                                L=L, use_graph=use_graph, adapt=adapt, target_accept=target_accept, ladder=ladder,
+                                beta_min=beta_min, swap_every=swap_every)
         self.epsilon, self.L = float(epsilon), int(L)
-        if self.L < 1:
-            raise ValueError("HMC needs L >= 1 leapfrog steps")
         super().__init__(op, sigma, seed, chain0, use_graph, groups, priorsigma)
-        # warm-up: `adapt` steps of dual averaging from `epsilon` towards `target_accept` (default 0.8; MALA 0.574) and, with
-        # adapt_mass, Stan's mass windows; 0: the fixed-step kernels
-        self.target_accept = TARGET_ACCEPT[self._kind] if target_accept is None else float(target_accept)
-        self.adapt = check_adapt_args(adapt, self.target_accept)
-        self.adapt_mass = bool(adapt_mass)
-        # replica exchange: the inverse temperatures of one ladder (None: no tempering) and the steps between exchange rounds
-        self.beta_min, self.swap_every = float(beta_min), swap_every
-        self._ladder = None if ladder is None else check_temper_args(ladder, beta_min, swap_every, chain0=self.chain0,
-                                                                     use_graph=self.use_graph)
-        # hierarchical prior: the settings (None: the scalar prior or none) and the weight groups, known before any launch
-        self._hyper = check_hyperprior(hyperprior)
-        self.prior_groups = None
-        if self._hyper is not None:
-            if self._ladder is not None:
-                raise ValueError("hyperprior does not run with a ladder (a tempered rung would need its own precisions)")
-            if self.use_graph:
-                raise ValueError("hyperprior does not run with use_graph=True (the round counter changes from launch to launch)")
-            seg, names = group_segments(op.arch, self._hyper['groups'])
-            self._seg = check_segments(seg, op.p)
-            initial_tau(self._hyper, len(names), self.priorsigma)              # (a tau0 of the wrong length is refused here)
-            self.prior_groups = [(n, int(lo), int(hi)) for n, lo, hi in zip(names, seg[:-1], seg[1:])]
-        # noise prior: the settings (None: the hand-set noise level `sigma`)
-        self._noise = check_noiseprior(noiseprior)
-        if self._noise is not None:
-            if self._ladder is not None:
-                raise ValueError("noiseprior does not run with a ladder (a tempered rung would need its own noise level)")
-            if self.use_graph:
-                raise ValueError("noiseprior does not run with use_graph=True (the round counter changes from launch to launch)")
-            if type(op.arch).__name__ != 'MLPArch':
-                raise ValueError(f"noiseprior: the noise level is sampled for plain MLPs, not for {type(op.arch).__name__}")
-            if op.tdt != torch.float64:
-                raise ValueError("noiseprior needs a float64 operator (the fold's rescaling of a float32 gradient would round it "
-                                 "a second time)")
+        self.target_accept, self.adapt, self.adapt_mass = cfg['target_accept'], cfg['adapt'], bool(adapt_mass)
+        self.beta_min, self.swap_every = float(beta_min), swap_every           # (the steps between two exchange rounds)
+        self._ladder, self._hyper, self._noise = cfg['ladder'], cfg['hyperprior'], cfg['noiseprior']
+        self._seg, self.prior_groups = cfg['seg'], cfg['prior_groups']
 
     def _begin(self, s, st):
         """Enqueue the begin call of a step.  The entry point follows from what the state holds: s['beta'] (a ladder) -> _t,
@@ -255,11 +262,6 @@ class DeviceHMC(DeviceEngine):
                                         a['n'], s['da'].data_ptr(), s['eps'].data_ptr(), _ptr(s['wmean']), _ptr(s['wm2']),
                                         _ptr(s['scale']), self._stream()), "qn_hmc_adapt")
 
-    def _ngroups(self, C):
-        if self.groups is None:
-            return 1
-        return min(self.groups, C)
-
     def _clone(self, op, chain0):
         return DeviceHMC(op, self.sigma, self.epsilon, self.L, self.seed, chain0, self.use_graph, groups=1, adapt=self.adapt,
                          target_accept=self.target_accept, adapt_mass=self.adapt_mass, ladder=self._ladder,
@@ -272,18 +274,19 @@ class DeviceHMC(DeviceEngine):
             for g in range(G + 1):
                 check_whole_ladders(self._ladder.size, None, C * g // G)
 
-    def _merge_groups(self, out, res, engs):
+    def _extra_keys(self, nmcmc):
+        f64, keys = np.float64, {}
+        rounds = lambda every: nmcmc // every if every else 0
         if self.adapt:
-            out['epsilon'] = torch.cat([r['epsilon'] for r in res])
-            out['mass_scale'] = None if res[0]['mass_scale'] is None else torch.cat([r['mass_scale'] for r in res])
-            out['nwarm'] = self.adapt
+            mass = any(a['finish'] for a in warmup_plan(self.adapt, self.adapt_mass))
+            keys.update(epsilon=((), f64), mass_scale=((self.op.p,), f64) if mass else None, nwarm=self.adapt)
         if self._ladder is not None:
-            for k in ('beta', 'swap_rate', 'replica'):
-                out[k] = torch.cat([r[k] for r in res])
+            keys.update(beta=((), f64), swap_rate=((), f64), replica=((rounds(int(self.swap_every)) + 1,), np.int32))
         if self._hyper is not None:
-            out['tau'] = torch.cat([r['tau'] for r in res])
+            keys['tau'] = ((rounds(self._hyper['every']) + 1, len(self._seg) - 1), f64)
         if self._noise is not None:
-            out['sigma'] = torch.cat([r['sigma'] for r in res])
+            keys['sigma'] = ((rounds(self._noise['every']) + 1,), f64)
+        return keys
 
     def _hyper_state(self, C, nmcmc):
         """The run state of a hyper-prior (empty without one): per chain and group lam = sigma^2 tau and the constant c0,

@@ -52,29 +52,39 @@ class DeviceNUTS(DeviceEngine):
     adapt (warm-up steps of step-size dual averaging towards target_accept; no mass windows), block (iterations enqueued
     between two looks at the chains' step counters), plus the engine's priorsigma / seed / chain0 / groups."""
 
-    def __init__(self, op, sigma, epsilon=0.05, mass_scale=None, max_depth=10, adapt=0, target_accept=0.8, block=32, seed=0,
-                 chain0=0, groups=None, use_graph=False, ladder=None, priorsigma=None):
+    _kind = 'nuts'
+
+    @classmethod
+    def check_params(cls, arch, dtype, nmcmc, priorsigma, epsilon=0.05, max_depth=10, adapt=0, target_accept=0.8, block=32,
+                     use_graph=False, ladder=None, **rest):
+        cfg = super().check_params(arch, dtype, nmcmc, priorsigma, **rest)
         if use_graph:
             raise ValueError("DeviceNUTS with use_graph=True: the number of iterations of a run is data dependent, there is no "
                              "fixed launch sequence to capture; run with use_graph=False")
         if ladder is not None:
             raise ValueError("DeviceNUTS with ladder: the No-U-Turn sampler is not tempered; replica exchange is for "
                              "sampler='hmc' / 'mala'")
-        if op.tdt != torch.float64:
+        if dtype != 'float64':
             raise ValueError("DeviceNUTS needs a float64 operator: U-turn tests and energy errors along a trajectory of "
                              "hundreds of leapfrogs are made in float64 (build the operator with dtype='float64')")
+        cfg['nuts'] = check_nuts_args(epsilon, max_depth, adapt, target_accept, block, nmcmc)
+        return cfg
+
+    @classmethod
+    def shard_params(cls, sampler_params, lo, hi):
+        """The per-chain step sizes [C] and scales [C, p] of all chains: this rank's rows (a scalar step size is everyone's)."""
+        return {k: (np.asarray(v, dtype=np.float64)[lo:hi] if k in ('epsilon', 'mass_scale') and np.ndim(v) >= 1 else v)
+                for k, v in sampler_params.items()}
+
+    def __init__(self, op, sigma, epsilon=0.05, mass_scale=None, max_depth=10, adapt=0, target_accept=0.8, block=32, seed=0,
+                 chain0=0, groups=None, use_graph=False, ladder=None, priorsigma=None):
         if isinstance(epsilon, torch.Tensor):
             epsilon = epsilon.detach().cpu().numpy()
-        self.epsilon, self.max_depth, self.adapt, self.target_accept, self.block = check_nuts_args(
-            epsilon, max_depth, adapt, target_accept, block)
+        self.epsilon, self.max_depth, self.adapt, self.target_accept, self.block = self.check_params(
+            op.arch, op.dtype, None, priorsigma, epsilon=epsilon, max_depth=max_depth, adapt=adapt, target_accept=target_accept,
+            block=block, use_graph=use_graph, ladder=ladder)['nuts']
         self.mass_scale = mass_scale                               # (None, an array or a tensor: checked against C, p in the run)
         super().__init__(op, sigma, seed, chain0, False, groups, priorsigma)
-        self.last_iters = None                 # (diagnostics: iterations enqueued by the last run, and how many were needed)
-
-    def _ngroups(self, C):
-        if self.groups is None:
-            return 1
-        return min(self.groups, C)
 
     def _clone(self, op, chain0):
         lo = chain0 - self.chain0
@@ -82,11 +92,10 @@ class DeviceNUTS(DeviceEngine):
         return DeviceNUTS(op, self.sigma, cut(self.epsilon), cut(self.mass_scale), self.max_depth, self.adapt, self.target_accept,
                           self.block, self.seed, chain0, groups=1, priorsigma=self.priorsigma)
 
-    def _merge_groups(self, out, res, engs):
-        for k in ('depth', 'nleap', 'ndiv', 'ntreedepth', 'ngrad', 'epsilon'):
-            out[k] = torch.cat([r[k] for r in res])
-        out['nwarm'] = self.adapt
-        self.last_iters = [e.last_iters for e in engs]
+    def _extra_keys(self, nmcmc):
+        steps, count = ((nmcmc + 1,), np.int32), ((), np.int64)
+        return {'depth': steps, 'nleap': steps, 'ndiv': count, 'ntreedepth': count, 'ngrad': count, 'epsilon': ((), np.float64),
+                'nwarm': self.adapt}
 
     def _iter(self, s, nmcmc):
         """Enqueue one iteration on the current stream: the gradient at the pending points, the prior, then the decision."""
@@ -156,32 +165,7 @@ class DeviceNUTS(DeviceEngine):
             sse0.data_ptr(), eps0.data_ptr(), ptr(scale), self.sigma, self.op.N, C, self.chain0, p, self.seed,
             *(s[k].data_ptr() for k in self._VEC[:11]), s['zz'].data_ptr(), s['best_lp'].data_ptr(), s['es'].data_ptr(),
             s['ei'].data_ptr(), self._stream()), "qn_nuts_begin")
-        # the smallest step counter after each block: reduced on the device, copied into pinned memory behind the block, and
-        # looked at one block late -- when the next block is already enqueued
-        tmin_dev = torch.empty(2, dtype=torch.int64, device=dev)
-        tmin_host = torch.zeros(2, dtype=torch.int64).pin_memory()
-        events = [torch.cuda.Event(), torch.cuda.Event()]
-        bound = nmcmc * (2 ** self.max_depth - 1) + 2 * self.block
-        k = needed = 0
-        while True:
-            for _ in range(self.block):
-                self._iter(s, nmcmc)
-            torch.amin(s['ei'][s['par'], :, 0], dim=0, out=tmin_dev[k & 1])
-            tmin_host[k & 1].copy_(tmin_dev[k & 1], non_blocking=True)
-            events[k & 1].record(torch.cuda.current_stream(dev))
-            k += 1
-            yield
-            if k >= 2:
-                events[k & 1].synchronize()                        # block k - 2 (0-based): block k - 1 is already enqueued
-                tmin = int(tmin_host[k & 1])
-                if verbose:
-                    print('%d iterations enqueued, slowest chain at step %d / %d' % (k * self.block, tmin, nmcmc))
-                if tmin >= nmcmc:
-                    needed = (k - 1) * self.block
-                    break
-            if k * self.block >= bound:                            # (cannot happen: a step ends within 2^max_depth - 1 iterations)
-                raise _lib.QuinnAmdError("DeviceNUTS: the chains did not finish within nmcmc * (2^max_depth - 1) iterations")
-        self.last_iters = (k * self.block, needed)
+        yield from self._run_blocks(s, nmcmc, nmcmc * (2 ** self.max_depth - 1) + 2 * self.block, verbose)      # (a step: <= 2^max_depth - 1)
         par = s['par']
         es, ei = s['es'][par], s['ei'][par]
         return {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][par].clone(),

@@ -35,19 +35,24 @@ class DeviceSGHMC(DeviceEngine):
     weight prior N(0, s^2 I), folded into every minibatch call's SSE and gradient with the constants times Nb / N, so that the
     update's N / Nb leaves it unscaled: the prior is exact, only the likelihood is estimated)."""
 
+    _kind = 'sghmc'
+
+    @classmethod
+    def check_params(cls, arch, dtype, nmcmc, priorsigma, eta=1e-5, alpha=0.1, batch=None, thin=1, schedule='constant', cycles=1,
+                     explore_frac=0.0, temperature=1.0, **rest):
+        cfg = super().check_params(arch, dtype, nmcmc, priorsigma, **rest)
+        check_sg_args(eta, alpha, batch, thin, schedule, cycles, explore_frac, temperature, nmcmc)
+        return cfg
+
     def __init__(self, op, sigma, eta=1e-5, alpha=0.1, batch=None, thin=1, schedule='constant', cycles=1, explore_frac=0.0,
                  temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None, priorsigma=None):
-        check_sg_args(eta, alpha, batch, thin, schedule, cycles, explore_frac, temperature)
+        self.check_params(op.arch, op.dtype, None, priorsigma, eta=eta, alpha=alpha, batch=batch, thin=thin, schedule=schedule,
+                          cycles=cycles, explore_frac=explore_frac, temperature=temperature)
         self.eta, self.alpha = float(eta), float(alpha)
         self.batch = None if batch is None else int(batch)
         self.thin, self.schedule, self.cycles = int(thin), schedule, int(cycles)
         self.explore_frac, self.temperature = float(explore_frac), float(temperature)
         super().__init__(op, sigma, seed, chain0, use_graph, groups, priorsigma)
-
-    def _ngroups(self, C):
-        if self.groups is None:
-            return 1
-        return min(self.groups, C)
 
     def _clone(self, op, chain0):
         return DeviceSGHMC(op, self.sigma, self.eta, self.alpha, self.batch, self.thin, self.schedule, self.cycles,
@@ -133,6 +138,7 @@ class DeviceSGHMC(DeviceEngine):
 
 class DeviceSGLD(DeviceSGHMC):
     """Stochastic-gradient Langevin dynamics: `DeviceSGHMC` with alpha = 1 (no momentum array)."""
+    _kind = 'sgld'
 
     def __init__(self, op, sigma, eta=1e-5, batch=None, thin=1, schedule='constant', cycles=1, explore_frac=0.0,
                  temperature=1.0, seed=0, chain0=0, use_graph=False, groups=None, priorsigma=None):

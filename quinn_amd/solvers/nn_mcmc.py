@@ -22,29 +22,28 @@ from ..mcmc.admcmc import AMCMC
 from ..mcmc.hmc import HMC
 from ..mcmc.mala import MALA
 from ..mcmc.device_amcmc import DeviceAMCMC
+from ..mcmc.device_engine import priors_refusal
 from ..mcmc.device_hmc import DeviceHMC
 from ..mcmc.device_mala import DeviceMALA
 from ..mcmc.device_sgmcmc import DeviceSGHMC, DeviceSGLD
 from ..mcmc.device_ess import DeviceESS
-from ..mcmc.ess import check_ess_args
 from ..mcmc.device_nuts import DeviceNUTS
-from ..mcmc.nuts import check_nuts_args
 from ..mcmc import diagnostics as diag
 from ..mcmc import rankdiag
-from ..mcmc.tempering import check_temper_args, check_whole_ladders
+from ..mcmc.tempering import check_whole_ladders
 from ..mcmc.prior import check_priorsigma, grad_log_prior, log_prior
-from ..mcmc.hyper import check_hyperprior, group_segments, initial_tau
-from ..mcmc.noise import check_noiseprior
 from .. import scoring
 from ..ops import BatchedMLP, neg_log_post_from_sse, check_gradloss_args
-from ..parallel import adapt_keys, dist_info, empty_results, gather_results, run_chains_sharded, shard_bounds
+from ..parallel import dist_info, gather_results, run_chains_sharded, shard_bounds
 from .quinn import QUiNNBase
 
-# fit(engine='device'): sampler -> class
+# fit(engine='device'): sampler -> class (its `check_params` refuses what it cannot run, before any device is touched)
 DEVICE_ENGINES = {'amcmc': DeviceAMCMC, 'hmc': DeviceHMC, 'mala': DeviceMALA, 'sgld': DeviceSGLD, 'sghmc': DeviceSGHMC,
                   'ess': DeviceESS, 'nuts': DeviceNUTS}
 # stochastic-gradient samplers, elliptical slice sampling, the No-U-Turn sampler: no host counterpart
 DEVICE_ONLY = ('sgld', 'sghmc', 'ess', 'nuts')
+# fit(engine='host'): sampler -> (class, whether it takes the gradient hook)
+HOST_SAMPLERS = {'amcmc': (AMCMC, False), 'hmc': (HMC, True), 'mala': (MALA, True)}
 
 
 def _rank_keys(stats):
@@ -270,55 +269,31 @@ class NN_MCMC(QUiNNBase):
         """
         self.diagnostics = None
         priorsigma = check_priorsigma(priorsigma)
-        hyperprior = check_hyperprior(hyperprior)
-        if hyperprior is not None:                # (before any device is touched)
-            sp = dict(sampler_params or {})
-            if sampler not in ('hmc', 'mala') or engine != 'device':
-                raise ValueError(f"hyperprior runs with sampler='hmc' | 'mala' and engine='device' only (got sampler={sampler!r}, "
-                                 f"engine={engine!r})")
-            if sp.get('ladder') is not None:
-                raise ValueError("hyperprior does not run with a ladder (a tempered rung would need its own precisions)")
-            if sp.get('use_graph'):
-                raise ValueError("hyperprior does not run with use_graph=True (the round counter changes from launch to launch)")
-            if type(self.arch).__name__ != 'MLPArch':
-                raise ValueError("hyperprior: weight groups are defined for plain MLPs, not for a residual network (RNet)")
-            hseg, hnames = group_segments(self.arch, hyperprior['groups'])
-            initial_tau(hyperprior, len(hnames), priorsigma)
-        noiseprior = check_noiseprior(noiseprior)
-        if noiseprior is not None:                # (before any device is touched)
-            sp = dict(sampler_params or {})
-            if sampler not in ('hmc', 'mala') or engine != 'device':
-                raise ValueError(f"noiseprior runs with sampler='hmc' | 'mala' and engine='device' only (got sampler={sampler!r}, "
-                                 f"engine={engine!r})")
-            if sp.get('ladder') is not None:
-                raise ValueError("noiseprior does not run with a ladder (a tempered rung would need its own noise level)")
-            if sp.get('use_graph'):
-                raise ValueError("noiseprior does not run with use_graph=True (the round counter changes from launch to launch)")
-            if type(self.arch).__name__ != 'MLPArch':
-                raise ValueError("noiseprior: the noise level is sampled for plain MLPs, not for a residual network (RNet)")
-        if sampler in DEVICE_ONLY and engine != 'device':
-            raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host engine for it)")
-        if sampler == 'ess':                     # (before any device is touched)
-            sp = dict(sampler_params or {})
-            if priorsigma is None:
-                raise ValueError("sampler='ess' needs priorsigma: elliptical slice sampling draws from the Gaussian weight prior "
-                                 "N(0, priorsigma^2 I); pass fit(..., priorsigma=s) with s > 0")
-            check_ess_args(priorsigma, sp.get('max_shrink', 32), sp.get('block', 32))
-        if sampler == 'nuts':                    # (before any device is touched)
-            sp = dict(sampler_params or {})
-            check_nuts_args(sp.get('epsilon', 0.05), sp.get('max_depth', 10), sp.get('adapt', 0), sp.get('target_accept', 0.8),
-                            sp.get('block', 32), nmcmc)
+        if seeds is not None:
+            seeds = list(seeds)
+        if engine == 'device':                   # every refusal that host values decide, before any device is touched
+            if sampler not in DEVICE_ENGINES:
+                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld', 'sghmc', 'ess' and "
+                                 "'nuts'")
+            # (the chains of the run: the rows of a 2-D param_ini, else one per seed)
+            ctot = np.shape(param_ini)[0] if np.ndim(param_ini) > 1 else nchains if seeds is None else len(seeds)
+            cfg = DEVICE_ENGINES[sampler].check_params(self.arch, self._dtype, nmcmc, priorsigma, nchains=ctot,
+                                                       hyperprior=hyperprior, noiseprior=noiseprior, **(sampler_params or {}))
+        else:
+            if sampler in DEVICE_ONLY:
+                raise ValueError(f"sampler={sampler!r} runs on the GPU only: pass engine='device' (there is no host engine for it)")
+            for name, val in (('hyperprior', hyperprior), ('noiseprior', noiseprior)):
+                if val is not None:
+                    raise ValueError(priors_refusal(name, sampler, engine))
+            cfg = {'priorsigma': priorsigma}
         diag_nburn = nmcmc // 2 if diag_nburn is None else int(diag_nburn)
         ntrn_, outdim = ytrn.shape
         assert xtrn.shape[0] == ntrn_
         self.lpinfo = {'model': None, 'xd': xtrn, 'yd': [y for y in ytrn], 'ltype': 'classical',
                        'lparams': {'sigma': datanoise}}
-        if priorsigma is not None:
-            self.lpinfo['lparams']['priorsigma'] = priorsigma
-        if hyperprior is not None:
-            self.lpinfo['lparams']['hyperprior'] = hyperprior
-        if noiseprior is not None:
-            self.lpinfo['lparams']['noiseprior'] = noiseprior
+        for k in ('priorsigma', 'hyperprior', 'noiseprior'):
+            if cfg.get(k) is not None:
+                self.lpinfo['lparams'][k] = cfg[k]
         if gtrn is not None:
             if engine == 'device':
                 raise NotImplementedError("gradient observations (gtrn) need engine='host': the device samplers' accept "
@@ -330,7 +305,6 @@ class NN_MCMC(QUiNNBase):
         elif gradnoise is not None:
             raise ValueError("gradnoise goes with gtrn")
         if seeds is not None:
-            seeds = list(seeds)
             nchains = len(seeds)
             rngs = [np.random.RandomState(s) for s in seeds]
         elif nchains > 1:
@@ -358,83 +332,54 @@ class NN_MCMC(QUiNNBase):
         if nadapt > nmcmc:
             raise ValueError(f"sampler_params['adapt'] = {nadapt} warm-up steps exceed nmcmc = {nmcmc}")
         if engine == 'device':
-            op = self._operator(self.lpinfo)
-            ini2 = np.atleast_2d(param_ini)
-            ctot = ini2.shape[0]
-            rank, world = dist_info()
-            lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
-            seed0 = seeds[0] if seeds else 0
-            if sampler not in DEVICE_ENGINES:
-                raise ValueError("engine='device' is implemented for sampler='amcmc', 'hmc', 'mala', 'sgld', 'sghmc', 'ess' and "
-                                 "'nuts'")
-            # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
-            nrounds = None
-            if sampler_params.get('ladder') is not None and sampler in ('hmc', 'mala'):
-                # replica exchange: all chains, and this rank's shard of them, are whole ladders (refused before any launch)
-                R = check_temper_args(sampler_params['ladder'], sampler_params.get('beta_min', 0.01),
-                                      sampler_params.get('swap_every', 1), C=ctot,
-                                      use_graph=sampler_params.get('use_graph', False)).size
-                check_whole_ladders(R, hi - lo, lo)
-                nrounds = nmcmc // int(sampler_params.get('swap_every', 1))
-            if sampler == 'nuts':                # per-chain step sizes / scales of all chains: this rank's rows
-                for k in ('epsilon', 'mass_scale'):
-                    if np.ndim(sampler_params.get(k)) >= 1:
-                        sampler_params[k] = np.asarray(sampler_params[k], dtype=np.float64)[lo:hi]
-            if hyperprior is not None:
-                sampler_params['hyperprior'] = hyperprior
-            if noiseprior is not None:
-                sampler_params['noiseprior'] = noiseprior
-            eng = DEVICE_ENGINES[sampler](op, datanoise, seed=seed0, chain0=lo, priorsigma=priorsigma, **sampler_params)
-            if hi > lo:
-                res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0)
-            elif sampler == 'nuts':
-                res = empty_results(nmcmc, ini2.shape[1])
-                res.update(depth=np.zeros((0, nmcmc + 1), dtype=np.int32), nleap=np.zeros((0, nmcmc + 1), dtype=np.int32),
-                           ndiv=np.zeros(0, dtype=np.int64), ntreedepth=np.zeros(0, dtype=np.int64),
-                           ngrad=np.zeros(0, dtype=np.int64), epsilon=np.zeros(0), nwarm=nadapt)
-            else:
-                res = empty_results(nmcmc, ini2.shape[1], *adapt_keys(nadapt, sampler_params.get('adapt_mass', True)),
-                                    nrounds=nrounds)
-                if hyperprior is not None:
-                    nr = nmcmc // hyperprior['every'] if hyperprior['every'] else 0
-                    res['tau'] = np.zeros((0, nr + 1, len(hnames)))
-                if noiseprior is not None:
-                    res['sigma'] = np.zeros((0, (nmcmc // noiseprior['every'] if noiseprior['every'] else 0) + 1))
-                if sampler == 'ess':
-                    res.update(nev=np.zeros((0, nmcmc + 1), dtype=np.int32), ntrunc=np.zeros(0, dtype=np.int64),
-                               nevals=np.zeros(0, dtype=np.int64))
-            if diagnostics:
-                # from the engine's device tensors, before they are downloaded (or not: gather_chain='none'); of a
-                # replica-exchange run the cold chains only (rung 0 of every ladder: shards are whole ladders)
-                dch, dlp, dtot = res['chain'], res['logpost'], ctot
-                if nrounds is not None:
-                    if dch is None:
-                        raise ValueError("diagnostics=True needs the stored chain")
-                    cp = (lambda v: v.contiguous()) if isinstance(dch, torch.Tensor) else np.ascontiguousarray
-                    dch, dlp, dtot = cp(dch[::R]), cp(dlp[::R]), ctot // R        # (a copy of 1 / R of the chain)
-                self.diagnostics = self._fit_diagnostics(dch, dlp, diag_nburn, dtot, gather, rank=diagnostics == 'rank')
-            # the single collective, at the end, straight from the device tensors (world == 1: a device->host copy)
-            res = gather_results(res, ctot, gather, gather_chain)
-            self.mcmc_results = res
-            if np.ndim(param_ini) == 1:
-                self.mcmc_results = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in self.mcmc_results.items()}
-            if hyperprior is not None:
-                self.mcmc_results['prior_groups'] = [(n, int(a), int(b)) for n, a, b in zip(hnames, hseg[:-1], hseg[1:])]
-            self.samples, self.cmode = self.mcmc_results['chain'], self.mcmc_results['mapparams']
-            return
-        if sampler == 'amcmc':
-            mymcmc = AMCMC(**sampler_params)
-            mymcmc.setLogPostBatch(self.logpost_batch, None, lpinfo=self.lpinfo)
-        elif sampler == 'hmc':
-            mymcmc = HMC(**sampler_params)
-            mymcmc.setLogPostBatch(self.logpost_batch, self.logpostgrad_batch, lpinfo=self.lpinfo)
-        elif sampler == 'mala':
-            mymcmc = MALA(**sampler_params)
-            mymcmc.setLogPostBatch(self.logpost_batch, self.logpostgrad_batch, lpinfo=self.lpinfo)
+            self._fit_device(DEVICE_ENGINES[sampler], cfg, sampler_params, nmcmc, param_ini, seeds, gather, gather_chain,
+                             diagnostics, diag_nburn)
         else:
-            raise ValueError(f"sampler {sampler!r} is not one of 'amcmc', 'hmc', 'mala'")
+            self._fit_host(sampler, sampler_params, nmcmc, param_ini, seeds, rngs, gather, gather_chain, diagnostics, diag_nburn)
 
-        if rngs is not None and dist_info()[1] > 1:
+    def _fit_device(self, engine_cls, cfg, sampler_params, nmcmc, param_ini, seeds, gather, gather_chain, diagnostics, diag_nburn):
+        """The run of `fit(engine='device')` after the common prologue.  cfg: what the engine's `check_params` returned."""
+        ini2 = np.atleast_2d(param_ini)
+        ctot = ini2.shape[0]
+        rank, world = dist_info()
+        lo, hi = shard_bounds(ctot) if world > 1 else (0, ctot)      # chains shard over ranks
+        # replica exchange: this rank's shard of the chains, like all of them, is whole ladders (refused before any launch)
+        R = None if cfg.get('ladder') is None else cfg['ladder'].size
+        if R is not None:
+            check_whole_ladders(R, hi - lo, lo)
+        op = self._operator(self.lpinfo)
+        priors = {k: cfg[k] for k in ('hyperprior', 'noiseprior') if cfg.get(k) is not None}
+        # random streams are keyed by the GLOBAL chain id: results do not depend on the number of ranks
+        eng = engine_cls(op, self.lpinfo['lparams']['sigma'], seed=seeds[0] if seeds else 0, chain0=lo, priorsigma=cfg['priorsigma'],
+                         **engine_cls.shard_params(sampler_params, lo, hi), **priors)
+        res = eng.run(nmcmc, ini2[lo:hi], verbose=self.verbose and rank == 0) if hi > lo else eng.empty_results(nmcmc)
+        if diagnostics:
+            # from the engine's device tensors, before they are downloaded (or not: gather_chain='none'); of a
+            # replica-exchange run the cold chains only (rung 0 of every ladder: shards are whole ladders)
+            dch, dlp, dtot = res['chain'], res['logpost'], ctot
+            if R is not None:
+                if dch is None:
+                    raise ValueError("diagnostics=True needs the stored chain")
+                cp = (lambda v: v.contiguous()) if isinstance(dch, torch.Tensor) else np.ascontiguousarray
+                dch, dlp, dtot = cp(dch[::R]), cp(dlp[::R]), ctot // R        # (a copy of 1 / R of the chain)
+            self.diagnostics = self._fit_diagnostics(dch, dlp, diag_nburn, dtot, gather, rank=diagnostics == 'rank')
+        # the single collective, at the end, straight from the device tensors (world == 1: a device->host copy)
+        self.mcmc_results = gather_results(res, ctot, gather, gather_chain)
+        if np.ndim(param_ini) == 1:
+            self.mcmc_results = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in self.mcmc_results.items()}
+        if cfg.get('prior_groups') is not None:
+            self.mcmc_results['prior_groups'] = cfg['prior_groups']
+        self.samples, self.cmode = self.mcmc_results['chain'], self.mcmc_results['mapparams']
+
+    def _fit_host(self, sampler, sampler_params, nmcmc, param_ini, seeds, rngs, gather, gather_chain, diagnostics, diag_nburn):
+        """The run of `fit(engine='host')` after the common prologue."""
+        if sampler not in HOST_SAMPLERS:
+            raise ValueError(f"sampler {sampler!r} is not one of 'amcmc', 'hmc', 'mala'")
+        sampler_cls, with_grad = HOST_SAMPLERS[sampler]
+        mymcmc = sampler_cls(**sampler_params)
+        mymcmc.setLogPostBatch(self.logpost_batch, self.logpostgrad_batch if with_grad else None, lpinfo=self.lpinfo)
+        sharded = rngs is not None and dist_info()[1] > 1
+        if sharded:
             # chains shard over ranks; one all_gather of the result arrays at the end
             self.mcmc_results = run_chains_sharded(lambda: mymcmc, nmcmc, param_ini, seeds, verbose=False, gather=gather, gather_chain=gather_chain)
         else:
@@ -444,8 +389,7 @@ class NN_MCMC(QUiNNBase):
             ch, lp = np.asarray(self.mcmc_results['chain']), np.asarray(self.mcmc_results['logpost'])
             if ch.ndim == 2:
                 ch, lp = ch[None], lp[None]
-            sharded = rngs is not None and dist_info()[1] > 1
-            ctot = nchains if sharded else ch.shape[0]
+            ctot = len(seeds) if sharded else ch.shape[0]
             if sharded and ch.shape[0] == ctot:      # gathered chains: every rank reduces its own shard only
                 lo, hi = shard_bounds(ctot)
                 ch, lp = ch[lo:hi], lp[lo:hi]
