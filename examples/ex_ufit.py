@@ -27,7 +27,8 @@ run without a prior and a `laplace_ggn` fit with the same `priorsigma` -- the La
 `ess` is elliptical slice sampling on the device with the same `priorsigma=1.0` (`engine='device'`; MLP network): no step size, forward
 calls only; it prints the forward evaluations a step took,
 `nuts` is the No-U-Turn sampler on the device (`engine='device'`; MLP network): no trajectory length, the step size dual-averaged
-over the first tenth of the run; it prints the depth and the leapfrogs a step took,
+over the first tenth of the run; it prints the depth and the leapfrogs a step took; `nuts mass` adds the mass windows of NUTS's own
+warm-up (`adapt_mass=True`) and prints the range of the scales found,
 and the matplotlib output is replaced by a printed summary of the predictive mean / standard deviation.
 """
 import sys
@@ -55,7 +56,7 @@ def Sine(xx, datanoise=0.0):
     return yy
 
 
-def main(meth, quick=False, mlp=False):
+def main(meth, quick=False, mlp=False, mass=False):
     torch.set_default_dtype(torch.double)
     all_uq_options = ['amcmc', 'hmc', 'stack', 'quantiles', 'pt', 'sghmc', 'prior', 'hyper', 'noise', 'ess', 'nuts', 'vi', 'ens', 'rms', 'laplace', 'laplace_ggn', 'laplace_kron', 'laplace_evidence', 'swag']
     assert meth in all_uq_options, f'Pick among {all_uq_options}'
@@ -182,12 +183,15 @@ def main(meth, quick=False, mlp=False):
     elif meth == 'nuts':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='nuts', engine='device',
-                  sampler_params={'epsilon': 1e-3, 'adapt': 1000 // k, 'max_depth': 8}, seeds=range(8), diagnostics=True)
+                  sampler_params={'epsilon': 1e-3, 'adapt': 1000 // k, 'max_depth': 8, **({'adapt_mass': True} if mass else {})},
+                  seeds=range(8), diagnostics=True)
         predict = lambda x: uqnet.predict_ens(x, nens=100 // k * 2, nburn=1000 // k, chain='all')
         r = uqnet.mcmc_results
         print(f"  depth per step: mean {r['depth'][:, 1:].mean():.2f}, max {r['depth'].max()}; leapfrogs per step: mean "
               f"{r['nleap'][:, 1:].mean():.2f}; divergent steps {r['ndiv'].sum()}, stopped by max_depth {r['ntreedepth'].sum()}; "
               f"step sizes {r['epsilon'].min():.3g} .. {r['epsilon'].max():.3g}; acceptance statistic {r['accrate'].mean():.3f}")
+        if r.get('mass_scale') is not None:
+            print(f"  mass windows: scales {r['mass_scale'].min():.3g} .. {r['mass_scale'].max():.3g}")
     elif meth == 'ess':
         uqnet = NN_MCMC(nnet, verbose=not quick)
         uqnet.fit(xtrn, ytrn, zflag=False, datanoise=datanoise, nmcmc=10000 // k, sampler='ess', engine='device',
@@ -272,4 +276,4 @@ def main(meth, quick=False, mlp=False):
 if __name__ == '__main__':
     torch.manual_seed(0)
     np.random.seed(0)
-    main(sys.argv[1], quick='--quick' in sys.argv, mlp='--mlp' in sys.argv)
+    main(sys.argv[1], quick='--quick' in sys.argv, mlp='--mlp' in sys.argv, mass='mass' in sys.argv[2:])

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libquinn_amd.so")
-SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_leap.hip", "qn_hmc_adapt.hip", "qn_temper.hip", "qn_sgmcmc.hip", "qn_prior.hip", "qn_hyper.hip", "qn_noise.hip", "qn_ess.hip", "qn_nuts.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip", "qn_score.hip", "qn_psis.hip", "qn_stack.hip", "qn_rank.hip", "qn_evidence.hip", "qn_quantile.hip"]
+SOURCES = ["qn_api.hip", "qn_generic.hip", "qn_fused.hip", "qn_fused_d8.hip", "qn_fused_o16.hip", "qn_fused_i8.hip", "qn_fused_bwd_i8.hip", "qn_wide_i8.hip", "qn_wide_u_i8.hip", "qn_dw_i8.hip", "qn_mcmc.hip", "qn_hmc_leap.hip", "qn_hmc_adapt.hip", "qn_temper.hip", "qn_sgmcmc.hip", "qn_prior.hip", "qn_hyper.hip", "qn_noise.hip", "qn_ess.hip", "qn_nuts.hip", "qn_nuts_adapt.hip", "qn_rnet.hip", "qn_curv.hip", "qn_glm.hip", "qn_sobolev.hip", "qn_swag.hip", "qn_kron.hip", "qn_diag.hip", "qn_score.hip", "qn_psis.hip", "qn_stack.hip", "qn_rank.hip", "qn_evidence.hip", "qn_quantile.hip"]
 # sources that #include another source (the second object of a file compiled in two parts): rebuilt when that one changes
 SOURCE_DEPS = {"qn_wide_u_i8.hip": ["qn_wide_i8.hip"], "qn_fused_d8.hip": ["qn_fused.hip"], "qn_fused_o16.hip": ["qn_fused.hip"]}
 
@@ -27,6 +27,7 @@ STACK_HEADER = os.path.join(_HERE, "..", "include", "quinn_amd_stack.h")  # ... 
 RANK_HEADER = os.path.join(_HERE, "..", "include", "quinn_amd_rank.h")    # ... and the rank-diagnostics extension's (csrc/qn_rank.hip)
 EV_HEADER = os.path.join(_HERE, "..", "include", "quinn_amd_evidence.h")  # ... and the Laplace-evidence extension's (csrc/qn_evidence.hip)
 QUANT_HEADER = os.path.join(_HERE, "..", "include", "quinn_amd_quantile.h")  # ... and the predictive-quantile extension's (csrc/qn_quantile.hip)
+NUTS_ADAPT_HEADER = os.path.join(_HERE, "..", "include", "quinn_amd_nuts_adapt.h")  # ... and the NUTS warm-up extension's (csrc/qn_nuts_adapt.hip)
 
 
 class QuinnAmdError(RuntimeError):
@@ -96,15 +97,18 @@ with open(EV_HEADER) as _f:
     EV_FUNCTIONS, _ev_constants = parse_header(_f.read())             # qn_la_evidence, qn_la_tune and their queries; QN_EV_*
 with open(QUANT_HEADER) as _f:
     QUANT_FUNCTIONS, _quant_constants = parse_header(_f.read())       # qn_pred_quantile, its workspace query; QN_QUANT_MAX_M / _Q / _ITER
+with open(NUTS_ADAPT_HEADER) as _f:
+    NUTS_ADAPT_FUNCTIONS, _nuts_adapt_constants = parse_header(_f.read())   # qn_nuts_adapt; QN_NUTS_PLAN_*
 QN_F64, QN_F32 = CONSTANTS["QN_F64"], CONSTANTS["QN_F32"]
 # keyed by the reference's activation names (quinn/nns/mlp.py:46-84)
 ACT_CODES = {"identity": CONSTANTS["QN_ACT_IDENTITY"], "tanh": CONSTANTS["QN_ACT_TANH"], "relu": CONSTANTS["QN_ACT_RELU"]}
-# PATH_AUTO .., ARITH_PLAIN .., CURV_HESS_FULL .., GLM_COV_FULL .., SWAG_INIT .., SCORE_LPPD .. SCORE_NOUT, LOO_NOUT, PSIS_MAX_M, RANK_MAX_S, QUANT_MAX_M ..: the headers'
+# PATH_AUTO .., ARITH_PLAIN .., CURV_HESS_FULL .., GLM_COV_FULL .., SWAG_INIT .., SCORE_LPPD .. SCORE_NOUT, LOO_NOUT, PSIS_MAX_M, RANK_MAX_S, QUANT_MAX_M .., NUTS_PLAN_COLLECT ..: the headers'
 # codes of these families under their names without the QN_ prefix
 globals().update((k[3:], v) for k, v in list(CONSTANTS.items()) + list(_psis_constants.items()) + list(_stack_constants.items()) +
-                 list(_rank_constants.items()) + list(_ev_constants.items()) + list(_quant_constants.items())
+                 list(_rank_constants.items()) + list(_ev_constants.items()) + list(_quant_constants.items()) +
+                 list(_nuts_adapt_constants.items())
                  if k.startswith(("QN_PATH_", "QN_ARITH_", "QN_CURV_", "QN_GLM_", "QN_SWAG_", "QN_SCORE_", "QN_LOO_", "QN_PSIS_",
-                                  "QN_STACK_", "QN_RANK_", "QN_EV_", "QN_QUANT_")))
+                                  "QN_STACK_", "QN_RANK_", "QN_EV_", "QN_QUANT_", "QN_NUTS_")))
 
 
 def build(force=False, verbose=False, jobs=None):
@@ -119,7 +123,7 @@ def build(force=False, verbose=False, jobs=None):
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
-           [HEADER, PSIS_HEADER, STACK_HEADER, RANK_HEADER, EV_HEADER, QUANT_HEADER]
+           [HEADER, PSIS_HEADER, STACK_HEADER, RANK_HEADER, EV_HEADER, QUANT_HEADER, NUTS_ADAPT_HEADER]
     hnew = max(os.path.getmtime(h) for h in hdrs)
     extra = os.environ.get("QN_HIPCC_FLAGS", "").split()          # A/B builds (-DQN_...)
     key = hashlib.sha1(" ".join(extra).encode()).hexdigest()[:10] if extra else ""
@@ -171,7 +175,8 @@ def lib():
                             "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(PSIS_FUNCTIONS.items()) + list(STACK_FUNCTIONS.items()) + \
-            list(RANK_FUNCTIONS.items()) + list(EV_FUNCTIONS.items()) + list(QUANT_FUNCTIONS.items()):
+            list(RANK_FUNCTIONS.items()) + list(EV_FUNCTIONS.items()) + list(QUANT_FUNCTIONS.items()) + \
+            list(NUTS_ADAPT_FUNCTIONS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -119,7 +119,7 @@ class DeviceEngine:
             yield
             if k >= 2:
                 events[k & 1].synchronize()                        # block k - 2 (0-based): block k - 1 is already enqueued
-                tmin = int(tmin_host[k & 1])
+                tmin = s['tmin'] = int(tmin_host[k & 1])            # (`_iter` may read it: what the host knows of the slowest chain)
                 if verbose:
                     print('%d iterations enqueued, slowest chain at step %d / %d' % (k * self.block, tmin, nmcmc))
                 if tmin >= nmcmc:

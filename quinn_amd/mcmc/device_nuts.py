@@ -6,7 +6,13 @@ There is no trajectory length: a step doubles its trajectory forwards or backwar
 diverges, or `max_depth` doublings are made), and takes its next point from the whole trajectory.  What remains to choose is
 the step size -- `adapt=K` dual-averages it over the first K steps -- and, optionally, a diagonal mass: pass the `mass_scale`
 [C, p] of a `DeviceHMC(adapt=...)` run as it is (its `epsilon` [C] too, but a step size tuned for a short L can be too large for
-trajectories of tens of leapfrogs: profiles/nuts.txt).  NUTS's own warm-up has no mass windows.
+trajectories of tens of leapfrogs: profiles/nuts.txt).  With `adapt_mass=True` NUTS's own warm-up also finds a per-chain diagonal
+mass over the slow windows of `quinn_amd.mcmc.adapt.warmup_schedule(adapt)` (`quinn_amd.mcmc.nuts_adapt` has the contract): the
+chains run on their own step counters, so one more launch per iteration, qn_nuts_adapt, looks every chain that has just ended a
+warm-up step up in a plan table on the device, dual-averages its step size (restarting at a window end), feeds or closes its
+window, and redoes the first half kick and drift of the step that has just started with the new step size and scale.
+qn_nuts_iter then runs with adapt = 0; the launch is dropped once the smallest step counter the host has seen is >= adapt.
+Without windows (adapt < 20) the run is that of adapt_mass=False.
 
 A step takes a data-dependent number of gradient evaluations, so the chains do not run in lock-step: every chain keeps its own
 step counter and its own tree on the device.  One iteration is one leapfrog of every live chain --
@@ -16,6 +22,7 @@ step counter and its own tree on the device.  One iteration is one leapfrog of e
     qn_nuts_iter         per chain: complete the leapfrog, test for divergence and U-turns from the checkpoints, then the next
                          leapfrog of the subtree, or merge the subtree and double, or end the step, store the row and start
                          the next step (two launches: reduce; decide and move)
+    qn_nuts_adapt        with adapt_mass and windows, during warm-up: step size, moments and scale of the chains that ended a step
 
 -- and every gradient evaluation is one some chain needs (a chain that has made its nmcmc steps idles).  Iterations are enqueued
 in blocks of `block`; after enqueuing block k + 1 the host reads the smallest step counter as of the end of block k (one 8-byte
@@ -29,10 +36,11 @@ operator's gradient array and the stored chain.
 Results: the common keys, with 'alphas' [C, nmcmc + 1] the acceptance statistic of each step (the mean of min(1, exp(-dE)) over
 its leaves; row 0 is 0) and 'accrate' its mean over the steps, plus 'depth' and 'nleap' [C, nmcmc + 1] int32 (doublings started
 and leapfrogs of each step), 'ndiv' (divergent steps), 'ntreedepth' (steps stopped by max_depth), 'ngrad' (= nleap summed) [C],
-'epsilon' [C] (the step sizes at the end) and 'nwarm' (= adapt).  Random streams are keyed by (seed, the chain's step, global
+'epsilon' [C] (the step sizes at the end; frozen after warm-up) and 'nwarm' (= adapt); with adapt_mass=True also 'mass_scale'
+[C, p], the scale the chains ended with (None without windows).  Random streams are keyed by (seed, the chain's step, global
 chain id): a chain does not depend on how the chains are split over ranks, engines or groups.
 
-Not here: mass windows in NUTS's own warm-up, tempering (`ladder`), graph capture (`use_graph`: the number of iterations is
+Not here: tempering (`ladder`), graph capture (`use_graph`: the number of iterations is
 data dependent), a host engine, float32 operators, and the extra U-turn checks across adjacent subtrees that Stan added later
 (the classic criterion on the tree and on every subtree is made).
 """
@@ -41,22 +49,26 @@ import torch
 
 from .. import _lib
 from .device_engine import DeviceEngine
+from .adapt import warmup_schedule
 from .nuts import check_nuts_args
+from .nuts_adapt import plan_table
 
-NES, NEI, NDOT = 12, 8, 27
+NES, NEI, NDOT, NWS = 12, 8, 27, 4
 
 
 class DeviceNUTS(DeviceEngine):
     """Args: epsilon (the step size: a scalar or [C], e.g. an `adapt` run's 'epsilon'), mass_scale (None, or [C, p]: the square
     root of the inverse diagonal mass per chain, e.g. an `adapt` run's 'mass_scale'), max_depth (doublings per step, 1 .. 12),
-    adapt (warm-up steps of step-size dual averaging towards target_accept; no mass windows), block (iterations enqueued
-    between two looks at the chains' step counters), plus the engine's priorsigma / seed / chain0 / groups."""
+    adapt (warm-up steps of step-size dual averaging towards target_accept), adapt_mass (True: the warm-up also finds a
+    per-chain diagonal mass over the windows of `warmup_schedule(adapt)`, starting from mass_scale or 1; needs adapt > 0),
+    block (iterations enqueued between two looks at the chains' step counters), plus the engine's priorsigma / seed / chain0 /
+    groups."""
 
     _kind = 'nuts'
 
     @classmethod
     def check_params(cls, arch, dtype, nmcmc, priorsigma, epsilon=0.05, max_depth=10, adapt=0, target_accept=0.8, block=32,
-                     use_graph=False, ladder=None, **rest):
+                     use_graph=False, ladder=None, adapt_mass=False, **rest):
         cfg = super().check_params(arch, dtype, nmcmc, priorsigma, **rest)
         if use_graph:
             raise ValueError("DeviceNUTS with use_graph=True: the number of iterations of a run is data dependent, there is no "
@@ -68,6 +80,12 @@ class DeviceNUTS(DeviceEngine):
             raise ValueError("DeviceNUTS needs a float64 operator: U-turn tests and energy errors along a trajectory of "
                              "hundreds of leapfrogs are made in float64 (build the operator with dtype='float64')")
         cfg['nuts'] = check_nuts_args(epsilon, max_depth, adapt, target_accept, block, nmcmc)
+        if not isinstance(adapt_mass, (bool, np.bool_)):
+            raise ValueError(f"adapt_mass = {adapt_mass!r}: True or False")
+        if adapt_mass and cfg['nuts'][2] == 0:
+            raise ValueError("DeviceNUTS with adapt_mass=True and adapt = 0: the mass windows are part of the warm-up; pass "
+                             "adapt=K warm-up steps (windows need K >= 20)")
+        cfg['nuts_adapt_mass'] = bool(adapt_mass)
         return cfg
 
     @classmethod
@@ -77,12 +95,13 @@ class DeviceNUTS(DeviceEngine):
                 for k, v in sampler_params.items()}
 
     def __init__(self, op, sigma, epsilon=0.05, mass_scale=None, max_depth=10, adapt=0, target_accept=0.8, block=32, seed=0,
-                 chain0=0, groups=None, use_graph=False, ladder=None, priorsigma=None):
+                 chain0=0, groups=None, use_graph=False, ladder=None, priorsigma=None, adapt_mass=False):
         if isinstance(epsilon, torch.Tensor):
             epsilon = epsilon.detach().cpu().numpy()
-        self.epsilon, self.max_depth, self.adapt, self.target_accept, self.block = self.check_params(
-            op.arch, op.dtype, None, priorsigma, epsilon=epsilon, max_depth=max_depth, adapt=adapt, target_accept=target_accept,
-            block=block, use_graph=use_graph, ladder=ladder)['nuts']
+        cfg = self.check_params(op.arch, op.dtype, None, priorsigma, epsilon=epsilon, max_depth=max_depth, adapt=adapt,
+                                target_accept=target_accept, block=block, use_graph=use_graph, ladder=ladder, adapt_mass=adapt_mass)
+        self.epsilon, self.max_depth, self.adapt, self.target_accept, self.block = cfg['nuts']
+        self.adapt_mass = cfg['nuts_adapt_mass']
         self.mass_scale = mass_scale                               # (None, an array or a tensor: checked against C, p in the run)
         super().__init__(op, sigma, seed, chain0, False, groups, priorsigma)
 
@@ -90,26 +109,42 @@ class DeviceNUTS(DeviceEngine):
         lo = chain0 - self.chain0
         cut = lambda a: a if a is None or isinstance(a, float) else a[lo:]      # (a group takes its rows from the front)
         return DeviceNUTS(op, self.sigma, cut(self.epsilon), cut(self.mass_scale), self.max_depth, self.adapt, self.target_accept,
-                          self.block, self.seed, chain0, groups=1, priorsigma=self.priorsigma)
+                          self.block, self.seed, chain0, groups=1, priorsigma=self.priorsigma, adapt_mass=self.adapt_mass)
 
     def _extra_keys(self, nmcmc):
         steps, count = ((nmcmc + 1,), np.int32), ((), np.int64)
-        return {'depth': steps, 'nleap': steps, 'ndiv': count, 'ntreedepth': count, 'ngrad': count, 'epsilon': ((), np.float64),
+        keys = {'depth': steps, 'nleap': steps, 'ndiv': count, 'ntreedepth': count, 'ngrad': count, 'epsilon': ((), np.float64),
                 'nwarm': self.adapt}
+        if self.adapt_mass:
+            keys['mass_scale'] = ((self.op.p,), np.float64) if self._windows() else None
+        return keys
+
+    def _windows(self):
+        """Whether the warm-up has mass windows: adapt_mass and a schedule with a window (adapt >= 20)."""
+        return self.adapt_mass and bool(warmup_schedule(self.adapt).ends)
 
     def _iter(self, s, nmcmc):
-        """Enqueue one iteration on the current stream: the gradient at the pending points, the prior, then the decision."""
+        """Enqueue one iteration on the current stream: the gradient at the pending points, the prior, then the decision; in a
+        warm-up with windows qn_nuts_iter makes no adaptation of its own (adapt = 0) and, until the slowest chain the host has
+        seen (s['tmin'], one block late) has left the warm-up, qn_nuts_adapt follows it."""
         C, p = s['cur'].shape
         self.op.sse_grad(s['q'], out=(s['sse'], s['gq']))
         if self._prior is not None:
             self.op.prior_fold(s['q'], *self._prior, sse=s['sse'], grad=s['gq'])
         ptr = lambda t: None if t is None else t.data_ptr()
         _lib.check(self._L.qn_nuts_iter(
-            s['sse'].data_ptr(), s['gq'].data_ptr(), ptr(s['scale']), self.sigma, self.op.N, self.max_depth, self.adapt,
+            s['sse'].data_ptr(), s['gq'].data_ptr(), ptr(s['scale']), self.sigma, self.op.N, self.max_depth,
+            0 if 'ws' in s else self.adapt,
             self.target_accept, C, self.chain0, p, nmcmc, self.seed, *(s[k].data_ptr() for k in self._VEC),
             s['best'].data_ptr(), s['best_lp'].data_ptr(), ptr(s['chain']), s['lps'].data_ptr(), s['alphas'].data_ptr(),
             s['depth'].data_ptr(), s['nleap'].data_ptr(), s['dots'].data_ptr(), s['zz'].data_ptr(), s['es'].data_ptr(),
             s['ei'].data_ptr(), s['par'], self._stream()), "qn_nuts_iter")
+        if 'ws' in s and s.get('tmin', 0) < self.adapt:
+            _lib.check(self._L.qn_nuts_adapt(
+                s['cur'].data_ptr(), s['alphas'].data_ptr(), nmcmc, self.adapt, self.target_accept, s['plan'].data_ptr(),
+                s['es'].data_ptr(), s['ei'].data_ptr(), s['par'], C, p, self.sigma, s['ql'].data_ptr(), s['ul'].data_ptr(),
+                s['gl'].data_ptr(), s['q'].data_ptr(), s['u'].data_ptr(), s['ws'].data_ptr(), s['mean'].data_ptr(),
+                s['m2'].data_ptr(), s['scale'].data_ptr(), self._stream()), "qn_nuts_adapt")
         s['par'] ^= 1
 
     _VEC = ('cur', 'gcur', 'ql', 'ul', 'gl', 'qr', 'ur', 'gr', 'rho', 'q', 'u', 'rho_sub', 'sub_q', 'sub_g', 'ck_u', 'ck_rho')
@@ -157,6 +192,12 @@ class DeviceNUTS(DeviceEngine):
                   'nleap': torch.zeros(C, nmcmc + 1, dtype=torch.int32, device=dev),
                   'dots': torch.zeros(C, nwg, NDOT, dtype=f64, device=dev), 'zz': torch.zeros(2, C, nwg, dtype=f64, device=dev),
                   'es': torch.zeros(2, C, NES, dtype=f64, device=dev), 'ei': torch.zeros(2, C, NEI, dtype=torch.int64, device=dev)})
+        if self._windows():                                        # the warm-up's own state: a writable scale, the plan, ws, moments
+            s['scale'] = scale = torch.ones(C, p, dtype=f64, device=dev) if scale is None else scale.clone()
+            s['plan'] = torch.as_tensor(plan_table(self.adapt), device=dev)
+            s['ws'] = torch.zeros(2, C, NWS, dtype=f64, device=dev)
+            s['ws'][0, :, 0], s['ws'][0, :, 3] = torch.log(10 * eps0), eps0
+            s['mean'], s['m2'] = torch.zeros(C, p, dtype=f64, device=dev), torch.zeros(C, p, dtype=f64, device=dev)
         if store_chain:
             s['chain'][:, 0] = cur
         s['lps'][:, 0] = lp0
@@ -168,7 +209,10 @@ class DeviceNUTS(DeviceEngine):
         yield from self._run_blocks(s, nmcmc, nmcmc * (2 ** self.max_depth - 1) + 2 * self.block, verbose)      # (a step: <= 2^max_depth - 1)
         par = s['par']
         es, ei = s['es'][par], s['ei'][par]
-        return {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][par].clone(),
-                'accrate': s['alphas'][:, 1:].mean(dim=1), 'logpost': s['lps'], 'alphas': s['alphas'], 'depth': s['depth'],
-                'nleap': s['nleap'], 'ndiv': ei[:, 5].clone(), 'ntreedepth': ei[:, 6].clone(), 'ngrad': ei[:, 7].clone(),
-                'epsilon': es[:, 0].clone(), 'nwarm': self.adapt}
+        out = {'chain': s['chain'], 'mapparams': s['best'], 'maxpost': s['best_lp'][par].clone(),
+               'accrate': s['alphas'][:, 1:].mean(dim=1), 'logpost': s['lps'], 'alphas': s['alphas'], 'depth': s['depth'],
+               'nleap': s['nleap'], 'ndiv': ei[:, 5].clone(), 'ntreedepth': ei[:, 6].clone(), 'ngrad': ei[:, 7].clone(),
+               'epsilon': es[:, 0].clone(), 'nwarm': self.adapt}
+        if self.adapt_mass:
+            out['mass_scale'] = s['scale'] if 'ws' in s else None
+        return out

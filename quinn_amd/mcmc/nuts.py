@@ -46,8 +46,8 @@ A subtree that diverges or turns is discarded: the proposal, rho and the edges k
 Step end: row t + 1 of chain (= cur), lps (= lp_cur), alphas (= sum_a / n_leap), depth (the doublings started: d, or d + 1 when
 the step ended inside a subtree) and nleap; ndiv += divergent; best <- cur where lp_cur >= best_lp; if t < adapt the step size
 is dual-averaged with the constants and the formula of `quinn_amd.mcmc.adapt` on a = sum_a / n_leap with m = t + 1, and frozen
-to exp(logbar) at t == adapt - 1 (step size only: NUTS has no mass windows of its own -- take `mass_scale` from an `adapt` run
-of HMC); t += 1 and, if t < nmcmc, the next step starts in the same iteration.  A chain with t == nmcmc is done: none of its
+to exp(logbar) at t == adapt - 1 (step size only; the warm-up with mass windows runs with adapt = 0 here and
+`quinn_amd.mcmc.nuts_adapt` behind every iteration); t += 1 and, if t < nmcmc, the next step starts in the same iteration.  A chain with t == nmcmc is done: none of its
 arrays is read or written.
 
 Random numbers: Philox4x32-10 keyed by (seed, stream = the chain's step t, [global chain id : 24][purpose : 4][index : 36]).

@@ -222,8 +222,9 @@ class NN_MCMC(QUiNNBase):
             momenta.  No trajectory length: a step doubles its trajectory until it turns back on itself.  sampler_params:
             epsilon (the step size, a scalar or one per chain), mass_scale (None, or `(nchains, p)`: e.g. 'mass_scale' of an
             'hmc' fit with adapt=K, with its 'epsilon'), max_depth (doublings per step, 1 .. 12; default 10), adapt (warm-up
-            steps of step-size dual averaging; NUTS's own warm-up has no mass windows), target_accept (default 0.8), block,
-            groups.  The chains advance asynchronously on the device; `mcmc_results` also holds 'depth' and 'nleap'
+            steps of step-size dual averaging), adapt_mass (default False; True: the warm-up also finds a per-chain diagonal
+            mass over the windows of `warmup_schedule(adapt)`, `quinn_amd.mcmc.nuts_adapt`, and `mcmc_results` holds
+            'mass_scale' `(C, p)`; needs adapt > 0), target_accept (default 0.8), block, groups.  The chains advance asynchronously on the device; `mcmc_results` also holds 'depth' and 'nleap'
             `(C, nmcmc + 1)` (doublings and leapfrogs per step), 'ndiv', 'ntreedepth', 'ngrad' and 'epsilon' `(C,)` and 'nwarm';
             'alphas' is the acceptance statistic of each step and 'accrate' its mean.  float64 operators only; no ladder, no
             graph capture.
